@@ -8,8 +8,13 @@ Data parallel: one process per GPU, each its own B utterances (weak scaling); th
 gradient is summed over ranks with RCCL all-reduce inside the timed step (§8e).  The optimizer
 step is excluded (§8d).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, ms_per_step).
+--dump-outputs DIR also writes what the last timed step returned (nll, logp, the flat gradient) as DIR/<name>.npy.
+--full adds the legs that take runs of their own: the optimizer step's time, the live per-kernel roofline, the
+rocprofv3 PMC passes and the CPU baseline (each still switched off by its --no-* option).
 """
 import argparse
 import json
@@ -80,6 +85,25 @@ def flops_per_utterance(cfg, L, T):
     p_step = S * Sc + O * S + A * S + 2 * S * S + 3 * S * 2 * S + (S + A) * M * k + M * O
     fwd = 2 * (L * (p_enc + A * Sc) + T * p_step + T * L * (2 * Sc + A))
     return 3 * fwd
+
+
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 1234
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: {name: tensor} of the last timed step written as directory/<name>.npy (float32).  The budget
+    is shared evenly; an array over its share is cut to a fixed sample of its flattened elements (indices drawn
+    once from DUMP_SAMPLE_SEED and the array's size, sorted), the same from run to run and build to build."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // (4 * len(arrays))  # elements per array
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, a.size, cap))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def cpu_worker(args):
@@ -315,12 +339,13 @@ def run_vgg(args, pmc, rank, world, torch, dist, s2s_amd, s2s_dist):
     def step():
         if args.no_graph:
             model.zeroGradParameters()
-            model.step(x, labels)
+            res = model.step(x, labels)
         else:
-            model.graph_step(x, labels)
+            res = model.graph_step(x, labels)
         if world > 1:  # one flat all-reduce per gradient tensor list (RCCL)
             for gt in grads:
                 dist.all_reduce(gt)
+        return res
 
     for _ in range(args.warmup):
         step()
@@ -330,12 +355,15 @@ def run_vgg(args, pmc, rank, world, torch, dist, s2s_amd, s2s_dist):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        nll, logp = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"nll": nll, "logp": logp,
+                                         "grads": torch.cat([gt.reshape(-1) for gt in grads])})
     if world > 1:
         t = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -422,7 +450,14 @@ def main():
     ap.add_argument("--flat-allreduce", action="store_true",
                     help="N>1: one all-reduce of the whole gradient after the step instead of the bucketed, "
                          "overlapped one")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: optimizer step time, live per-kernel "
+                         "roofline, rocprofv3 PMC passes, CPU baseline (default: the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's nll, logp and flat gradient as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu = args.no_kernel_timing = args.no_pmc = True
     if args.precision == "auto":
         args.precision = PRECISION.get(args.config, "fp32")
 
@@ -499,17 +534,18 @@ def main():
             xb, lb, flen, tlen = batches[it[0] % RAGGED_BATCHES]
             it[0] += 1
             real_frames[0] += sum(flen)
-            model.step(xb, lb, scale=scale, stream=stream, bucket_events=bucketed, frame_lengths=flen,
-                       label_lengths=tlen)
+            res = model.step(xb, lb, scale=scale, stream=stream, bucket_events=bucketed, frame_lengths=flen,
+                             label_lengths=tlen)
         else:
             real_frames[0] += B * L
-            model.step(x, labels, scale=scale, stream=stream, bucket_events=bucketed)
+            res = model.step(x, labels, scale=scale, stream=stream, bucket_events=bucketed)
         if bucketed:
             # per-bucket RCCL all-reduce issued as each bucket's gradients become final (decoder,
             # then encoder layers top-down), overlapping the BPTT of the layers below
             s2s_dist.allreduce_buckets(model.grads, buckets, wait=model.wait_bucket, comm_stream=comm)
         elif world > 1:
             s2s_dist.allreduce_gradients(model.grads)
+        return res
 
     with torch.cuda.stream(stream):
         for _ in range(args.warmup):
@@ -521,12 +557,18 @@ def main():
         t0 = time.perf_counter()
         real_frames[0] = 0
         for _ in range(args.steps):
-            step()
+            nll, logp = step()
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        if ragged:  # logp rows past an utterance's last label are padding the step leaves unwritten
+            logp = logp.clone()
+            for b, tb in enumerate(batches[(it[0] - 1) % RAGGED_BATCHES][3]):
+                logp[b, tb:] = 0
+        dump_outputs(args.dump_outputs, {"nll": nll, "logp": logp, "grads": model.grads})
     # a persistent launch that timed out would have produced invalid gradients: fail instead of reporting
     model.ctx.check_status(stream)
     if world > 1:
@@ -534,31 +576,32 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms = 1000.0 * elapsed / args.steps
-    # the optimizer (timit.lua:292-347: clip, adadelta, column-norm constraint) is outside t_step
-    #  and reported on its own: device step on the flat buffers, HBM-bound
-    opt = s2s_amd.optim.Adadelta(model, rho=0.95, eps=1e-8, colnormconstr=True)
-    flag = torch.zeros(1, dtype=torch.float32, device="cuda")
+    if args.full:
+        # the optimizer (timit.lua:292-347: clip, adadelta, column-norm constraint) is outside t_step
+        #  and reported on its own: device step on the flat buffers, HBM-bound
+        opt = s2s_amd.optim.Adadelta(model, rho=0.95, eps=1e-8, colnormconstr=True)
+        flag = torch.zeros(1, dtype=torch.float32, device="cuda")
 
-    def opt_step():
-        # data parallel: a failed persistent launch on ANY rank skips the update on every rank (the failure flag's MAX
-        # over the ranks, s2s_amd.dist.reduce_failure_flag), or the replicas diverge; one rank: the plain update
-        if world > 1:
-            opt.failure_flag(stream, out=flag)
-            s2s_dist.reduce_failure_flag(flag)
-            opt.step(stream, skip_flag=flag)
-        else:
-            opt.step(stream)
+        def opt_step():
+            # data parallel: a failed persistent launch on ANY rank skips the update on every rank (the failure flag's MAX
+            # over the ranks, s2s_amd.dist.reduce_failure_flag), or the replicas diverge; one rank: the plain update
+            if world > 1:
+                opt.failure_flag(stream, out=flag)
+                s2s_dist.reduce_failure_flag(flag)
+                opt.step(stream, skip_flag=flag)
+            else:
+                opt.step(stream)
 
-    with torch.cuda.stream(stream):
-        for _ in range(3):
-            opt_step()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(20):
-            opt_step()
-        e1.record(stream)
-    torch.cuda.synchronize()
-    opt_us = 1000.0 * e0.elapsed_time(e1) / 20
+        with torch.cuda.stream(stream):
+            for _ in range(3):
+                opt_step()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(20):
+                opt_step()
+            e1.record(stream)
+        torch.cuda.synchronize()
+        opt_us = 1000.0 * e0.elapsed_time(e1) / 20
     frames_per_step = world * real_frames[0] / args.steps  # every rank runs the same batch schedule
     value = frames_per_step / (ms / 1000.0)
 
@@ -582,10 +625,13 @@ def main():
                    "launch": "eager" if args.no_graph else "hipGraph replay",
                    "flop_per_step_per_gpu": flop_step},
         "step_tflops_per_gpu": round(flop_step / (ms / 1000.0) / 1e12, 3),
-        "optimizer": {"us_per_step": round(opt_us, 2), "what": "adadelta (rho .95, eps 1e-8) + global-norm clip + "
-                      "column-norm constraint on the flat buffers (s2s_optim_adadelta_step), not in ms_per_step; N > 1: "
-                      "behind the failure flag's MAX over the ranks (skipped on every rank if any rank's step failed)"},
     }
+    if args.full:
+        out["optimizer"] = {
+            "us_per_step": round(opt_us, 2),
+            "what": "adadelta (rho .95, eps 1e-8) + global-norm clip + column-norm constraint on the flat buffers "
+                    "(s2s_optim_adadelta_step), not in ms_per_step; N > 1: behind the failure flag's MAX over the "
+                    "ranks (skipped on every rank if any rank's step failed)"}
     if ragged:
         out["config"]["ragged"] = {
             "batches": RAGGED_BATCHES, "utterances": B * RAGGED_BATCHES,

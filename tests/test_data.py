@@ -64,24 +64,21 @@ def test_timit_layouts(tmp_path):
     assert (ds39["y"][10] == var["valid/10/y39"]).all()
 
 
-PYTABLES_TESTS = "/opt/conda/lib/python3.9/site-packages/tables/tests"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def test_hdf5_reader_known_answers():
-    """s2s_amd.hdf5 on real HDF5 files written by the HDF5 C library (PyTables' own test files, shipped in
-    this image's conda tree): float.h5 holds (5, 6) arrays arange(6) + arange(5)[:, None] in float16/32/64
-    (tables/tests/test_types.py ReadFloatTestCase); python3.h5 has datasets inside a subgroup."""
-    import os
+    """s2s_amd.hdf5 on real HDF5 files written by the HDF5 C library (two of PyTables' own test files, stored
+    under tests/golden/): pytables_float.h5 (tables/tests/float.h5) holds (5, 6) arrays
+    arange(6) + arange(5)[:, None] in float16/32/64 (tables/tests/test_types.py ReadFloatTestCase);
+    pytables_python3.h5 (tables/tests/python3.h5) has datasets inside a subgroup."""
     from s2s_amd import data, hdf5
-    fp = os.path.join(PYTABLES_TESTS, "float.h5")
-    if not os.path.exists(fp):
-        pytest.skip("no HDF5 sample files in this image")
-    t = hdf5.read_tree(fp)
+    t = hdf5.read_tree(os.path.join(GOLDEN, "pytables_float.h5"))
     ref = np.arange(6) + np.arange(5)[:, None]
     for dt in ("float16", "float32", "float64"):
         assert t[dt].dtype == np.dtype(dt) and t[dt].shape == (5, 6)
         np.testing.assert_array_equal(t[dt], ref.astype(dt))
-    t = data._read_tree(os.path.join(PYTABLES_TESTS, "python3.h5"))
+    t = data._read_tree(os.path.join(GOLDEN, "pytables_python3.h5"))
     assert t["agroup/anarray1"].shape == (7,) and t["agroup/anarray2"].shape == (1,)
 
 

@@ -8,5 +8,5 @@ out=$root/gpurun_out/prof_$r
 mkdir -p "$out"
 cd /tmp
 for c in timit_chorowski_dropout_b64 librispeech_chorowski_b32 librispeech_vgg_b16 timit_ragged_b32; do
-  timeout -k 10 400 python "$root/bench.py" --config $c > "$out/bench_$c.json"
+  timeout -k 10 400 python "$root/bench.py" --full --config $c > "$out/bench_$c.json"
 done

@@ -17,12 +17,12 @@ grep -E "^(CPU\(s\)|Model name|Thread|Core|Socket)" "$src/host_cpu.txt" > "$dst/
 for f in "$src"/bench_*.json; do [ -f "$f" ] && cp "$f" "$dst/"; done
 cat > "$dst/command.txt" <<TXT
 # produced by tools/profile_round.sh $r on one MI355X (gpurun), collected by tools/profile_collect.sh
-# bench line (driver command):             python bench.py
-# kernel trace + stats (kernel_stats.csv):  rocprofv3 --kernel-trace --stats --output-format csv -d .../trace -o prof -- python bench.py --steps 10 --warmup 2 --no-cpu --no-pmc
+# bench line (driver command):             python bench.py --full
+# kernel trace + stats (kernel_stats.csv):  rocprofv3 --kernel-trace --stats --output-format csv -d .../trace -o prof -- python bench.py --full --steps 10 --warmup 2 --no-cpu --no-pmc
 # HBM traffic (pmc_hbm.csv), two passes:    rocprofv3 --pmc FETCH_SIZE --output-format csv -- python bench.py --steps 2 --warmup 1 --no-cpu --no-kernel-timing --no-pmc --no-graph
 #                                           rocprofv3 --pmc WRITE_SIZE --output-format csv -- python bench.py --steps 2 --warmup 1 --no-cpu --no-kernel-timing --no-pmc --no-graph
 # MFMA evidence (pmc_mfma.csv), one pass:   rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -- python bench.py --steps 2 --warmup 1 --no-cpu --no-kernel-timing --no-pmc --no-graph
 # per-phase stamps (stamps_*.txt):          python tools/gru_stamps.py; python tools/xdec_stamps.py
-# secondary bench lines (bench_<config>.json): tools/bench_lines.sh (python bench.py --config <config>)
+# secondary bench lines (bench_<config>.json): tools/bench_lines.sh (python bench.py --full --config <config>)
 TXT
 echo "collected $src -> $dst"
