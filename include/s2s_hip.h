@@ -396,6 +396,74 @@ int s2s_optim_adadelta_step_flag(s2s_ctx* ctx, s2s_stream_t stream, const s2s_op
  * W_z/W_r/W_h, Wm, Wo) as (offset, rows, cols) triples; returns their count (mats may be NULL) */
 int s2s_model_weight_matrices(const s2s_model_dims* d, long* mats);
 
+/* ---------------------------------------------------------------- weight noise / adaptive weight noise
+ * nn.WeightNoise(parameters, sigma) and nn.AdaptiveWeightNoise(parameters, lambda, sigma_init) (WeightNoise.lua,
+ * AdaptiveWeightNoise.lua) with the trainer code around them (timit/timit.lua:190-205, 219-253, 291-333, 375-379),
+ * on the flat buffers of n elements, stream-ordered, no host sync.
+ *   adaptive = 1: weight = [mu ; s] (2n floats), s = log sigma^2; gradWeight = [gradmu ; grads] (2n).
+ *     lambda = the KL multiplier (opt.adalambda, 1/B); sigma = sigma_init (opt.adasigmainit).
+ *   adaptive = 0: weight, gradWeight (n floats); sigma = opt.weightnoise; lambda unused.
+ * The optimizer then updates `weight` with `gradWeight` (timit.lua:336-341; s2s_optim_adadelta_step on 2n or n
+ * elements with maxnorm = 1e20, weightDecay = 0, gradnoise_eta = 0: the clip, L2 and gradient noise belong to
+ * s2s_wnoise_backward).  With mats = s2s_model_weight_matrices its column-norm constraint lands on the rows of
+ * mu (the matrix offsets index the first n elements); the reference's lands on the sampled copy the next
+ * Sample() overwrites (timit.lua:344-346).
+ * state: s2s_wnoise_state_bytes() of device memory, zeroed by s2s_wnoise_reset.  Its first two 32-bit words are
+ * the sample counter t_s and the gradient-noise counter gradnoise.t, in that order: a checkpoint copies these 8
+ * bytes out and hands them back to s2s_wnoise_set_steps.
+ * The normals are the optimizer's counter-based ones, a function of (seed, counter, element): the sample of
+ * call t_s is the same for every launch geometry and data-parallel rank.  sample_seed must differ from
+ * gradnoise_seed when both noises are on (equal seeds and counters would draw the same normals twice). */
+typedef struct {
+  int adaptive;
+  float lambda, sigma;
+  float maxnorm, weightDecay;
+  float gradnoise_eta, gradnoise_gamma;
+  unsigned long long gradnoise_seed;
+  unsigned long long sample_seed;
+} s2s_wnoise_config;
+size_t s2s_wnoise_state_bytes(void);
+int s2s_wnoise_reset(s2s_ctx* ctx, s2s_stream_t stream, void* state);
+/* counters of a resumed run: the next sample draws with t_sample + 1, the next noised backward with
+ * t_gradnoise + 1 (gradnoise.t, timit/timit.lua:92, 312) */
+int s2s_wnoise_set_steps(s2s_ctx* ctx, s2s_stream_t stream, void* state, unsigned t_sample, unsigned t_gradnoise);
+/* the constructors: mu <- parameters, s <- log(sigma_init^2) (AdaptiveWeightNoise.lua:5-19, 40-56) /
+ * weight <- parameters (WeightNoise.lua:5-11) */
+int s2s_wnoise_init(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* params,
+                    float* weight, size_t n);
+/* parameters:copy(Sample()) (timit.lua:241-252): t_s += 1; params = mu + exp(s)^0.5 * N(0, 1)
+ * (AdaptiveWeightNoise.lua:27-38) / weight + sigma * N(0, 1) (WeightNoise.lua:17-22).  ONE draw per call: the
+ * reference draws per utterance inside its minibatch loop, a batched step draws once per minibatch (the same
+ * thing at B = 1). */
+int s2s_wnoise_sample(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* weight,
+                      float* params, size_t n, void* state);
+/* timit.lua:291-333 after the backward of the model step (whose `scale` is the 1/B of :292-295), with params
+ * still holding the sample and nll the step's (B) device losses:
+ *   ||g||, clip to maxnorm (:297-302); g += weightDecay * params and nll += 0.5 weightDecay ||params||^2
+ *   (:305-308); gradient noise (:310-315, the counter in `state`); then the module's forward + backward --
+ *   adaptive, lambda > 0 (AdaptiveWeightNoise.lua:63-104):
+ *     alpha_mu = mean(mu); alpha_sigma2 = max(1e-12, mean(exp s) + sum((mu - alpha_mu)^2) / n)
+ *     KL = 0.5 (n log alpha_sigma2 - sum s) + 0.5 / alpha_sigma2 (sum((mu - alpha_mu)^2) + sum(exp s)) - n / 2
+ *     L = lambda KL + nll;  gradmu = g + lambda (mu - alpha_mu) / alpha_sigma2
+ *     grads = 0.5 g^2 exp(s) + lambda 0.5 exp(s) / alpha_sigma2 - lambda 0.5
+ *   adaptive, lambda <= 0: L = nll, gradmu = g, grads = 0.5 g^2 exp(s) (KL, alpha_mu, alpha_sigma2 read 0, 0, 1);
+ *   fixed (WeightNoise.lua:28-35): L = nll, gradWeight = g.
+ * grads is left clipped / decayed / noised in place.  out: 6 device floats {L, mean nll (+ the L2 term), KL,
+ * ||g|| before clipping, alpha_mu, alpha_sigma2}.  The sums are taken in double in a fixed order (bitwise
+ * repeatable).  If the context's failure status is set when this runs on the device, or *skip_flag != 0 (the
+ * _flag form; see s2s_optim_adadelta_step_flag), the call is skipped there: grads, gradWeight and the counters
+ * stay untouched and only out[3] is written. */
+int s2s_wnoise_backward(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* weight,
+                        const float* params, float* grads, float* gradWeight, size_t n, const float* nll, int B,
+                        void* state, float* out);
+int s2s_wnoise_backward_flag(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* weight,
+                             const float* params, float* grads, float* gradWeight, size_t n, const float* nll,
+                             int B, void* state, float* out, const float* skip_flag);
+/* parameters:copy(Mode()) before evaluation (timit.lua:375-379): params = mu (AdaptiveWeightNoise.lua:58-61) /
+ * weight (WeightNoise.lua:24-26) */
+int s2s_wnoise_mode(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* weight,
+                    float* params, size_t n);
+
 /* ---------------------------------------------------------------- live kernel timing
  * s2s_prof_enable(1): every subsequent eager (non-captured) launch is bracketed by two
  * hipEvents on its stream and tagged with its kernel family's algorithmic flops/bytes.

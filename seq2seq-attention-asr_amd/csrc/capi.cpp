@@ -1376,6 +1376,87 @@ int s2s_ctx_status_flag(s2s_ctx* ctx, s2s_stream_t stream, float* flag) {
   return status_flag(static_cast<hipStream_t>(stream), ctx->status_dev, flag);
 }
 
+// ---------------------------------------------------------------- weight noise (wnoise.hip)
+// arguments are checked before the context so a bad call is named even where no context can exist
+static int wnoise_config(const s2s_wnoise_config* cfg, WnoiseConfig* c) {
+  S2S_REQUIRE(cfg != nullptr, "wnoise: null config");
+  S2S_REQUIRE(cfg->adaptive == 0 || cfg->adaptive == 1, "wnoise: adaptive must be 0 or 1");
+  S2S_REQUIRE(cfg->sigma >= 0.f && (!cfg->adaptive || cfg->sigma > 0.f), "wnoise: bad sigma");
+  S2S_REQUIRE(cfg->maxnorm > 0.f && cfg->weightDecay >= 0.f && cfg->gradnoise_eta >= 0.f, "wnoise: bad config");
+  S2S_REQUIRE(cfg->gradnoise_eta == 0.f || cfg->gradnoise_seed != cfg->sample_seed,
+              "wnoise: sample_seed must differ from gradnoise_seed when both noises are on");
+  *c = WnoiseConfig{cfg->adaptive,      cfg->lambda,          cfg->sigma,          cfg->maxnorm,    cfg->weightDecay,
+                    cfg->gradnoise_eta, cfg->gradnoise_gamma, cfg->gradnoise_seed, cfg->sample_seed};
+  return 0;
+}
+
+size_t s2s_wnoise_state_bytes(void) { return wnoise_state_bytes(); }
+
+int s2s_wnoise_reset(s2s_ctx* ctx, s2s_stream_t stream, void* state) {
+  S2S_REQUIRE(state != nullptr, "wnoise: null state");
+  S2S_TRY(set_device(ctx));
+  return wnoise_state_reset(static_cast<hipStream_t>(stream), state);
+}
+
+int s2s_wnoise_set_steps(s2s_ctx* ctx, s2s_stream_t stream, void* state, unsigned t_sample, unsigned t_gradnoise) {
+  S2S_REQUIRE(state != nullptr, "wnoise: null state");
+  S2S_TRY(set_device(ctx));
+  return wnoise_set_steps(static_cast<hipStream_t>(stream), state, t_sample, t_gradnoise);
+}
+
+int s2s_wnoise_init(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* params,
+                    float* weight, size_t n) {
+  WnoiseConfig c;
+  S2S_TRY(wnoise_config(cfg, &c));
+  S2S_REQUIRE(params && weight && n > 0, "wnoise_init: null argument");
+  S2S_TRY(set_device(ctx));
+  return wnoise_init(static_cast<hipStream_t>(stream), c, params, weight, n);
+}
+
+int s2s_wnoise_sample(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* weight,
+                      float* params, size_t n, void* state) {
+  WnoiseConfig c;
+  S2S_TRY(wnoise_config(cfg, &c));
+  S2S_REQUIRE(weight && params && state && n > 0, "wnoise_sample: null argument");
+  S2S_TRY(set_device(ctx));
+  return wnoise_sample(static_cast<hipStream_t>(stream), c, weight, params, n, state);
+}
+
+static int wnoise_bwd(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* weight,
+                      const float* params, float* grads, float* gradWeight, size_t n, const float* nll, int B,
+                      void* state, float* out, const float* skip_flag) {
+  WnoiseConfig c;
+  S2S_TRY(wnoise_config(cfg, &c));
+  S2S_REQUIRE(weight && params && grads && gradWeight && nll && state && out && n > 0,
+              "wnoise_backward: null argument");
+  S2S_REQUIRE(B > 0, "wnoise_backward: B must be positive");
+  S2S_TRY(set_device(ctx));
+  // device-side guard, as the optimizer's: skipped if the context's failure status (or *skip_flag) is set when it runs
+  return wnoise_backward(static_cast<hipStream_t>(stream), c, weight, params, grads, gradWeight, n, nll, B, state,
+                         out, ctx->status_dev, skip_flag);
+}
+
+int s2s_wnoise_backward(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* weight,
+                        const float* params, float* grads, float* gradWeight, size_t n, const float* nll, int B,
+                        void* state, float* out) {
+  return wnoise_bwd(ctx, stream, cfg, weight, params, grads, gradWeight, n, nll, B, state, out, nullptr);
+}
+
+int s2s_wnoise_backward_flag(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* weight,
+                             const float* params, float* grads, float* gradWeight, size_t n, const float* nll,
+                             int B, void* state, float* out, const float* skip_flag) {
+  return wnoise_bwd(ctx, stream, cfg, weight, params, grads, gradWeight, n, nll, B, state, out, skip_flag);
+}
+
+int s2s_wnoise_mode(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* weight,
+                    float* params, size_t n) {
+  WnoiseConfig c;
+  S2S_TRY(wnoise_config(cfg, &c));
+  S2S_REQUIRE(weight && params && n > 0, "wnoise_mode: null argument");
+  S2S_TRY(set_device(ctx));
+  return wnoise_mode(static_cast<hipStream_t>(stream), weight, params, n);
+}
+
 int s2s_model_bucket_count(const s2s_model_dims* d) {
   if (check_model_dims(d) != 0) return -1;
   return d->numLayers + 1;

@@ -14,6 +14,7 @@
 // The reference draws the noise with torch.randn; here it is a counter-based normal of (seed, t, i)
 // (splitmix64 -> Box-Muller), so any launch geometry -- and every data-parallel rank, which all hold
 // the same all-reduced gradients -- draws the same noise.
+#include "noise.h"  // mix64, noise_normal (shared with wnoise.hip)
 #include "s2s_common.h"
 
 #include <algorithm>
@@ -52,24 +53,6 @@ __global__ __launch_bounds__(256) void opt_sumsq(const float* __restrict__ g, si
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-constexpr unsigned long long kGolden = 0x9e3779b97f4a7c15ull;
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-
-// N(0, 1) for element i of the step keyed by mix64(seed * kGolden + t): u1 in (0, 1], u2 in [0, 1)
-// from 24-bit fields of mix64(key + i * kGolden), z = sqrt(-2 ln u1) cos(2 pi u2)
-// (oracle/s2s_oracle.py: gradient_noise restates it)
-__device__ __forceinline__ float noise_normal(unsigned long long key, size_t i) {
-  const unsigned long long h = mix64(key + (unsigned long long)i * kGolden);
-  const float u1 = (float)((h >> 40) + 1) * (1.0f / 16777216.0f);
-  const float u2 = (float)((h >> 16) & 0xffffffull) * (1.0f / 16777216.0f);
-  return sqrtf(-2.f * logf(u1)) * cosf(6.28318530717958647692f * u2);
 }
 
 // status: the context's failure words (handoff.h; host-coherent, written by the step's harvest kernel earlier

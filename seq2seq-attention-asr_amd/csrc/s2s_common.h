@@ -298,4 +298,20 @@ int optim_adadelta_step(hipStream_t st, const OptimConfig& c, float* x, float* g
                         const unsigned* status = nullptr, const float* skip_flag = nullptr);
 int status_flag(hipStream_t st, const unsigned* status, float* flag);
 
+// ---------------------------------------------------------------- weight noise (wnoise.hip)
+struct WnoiseConfig {
+  int adaptive;
+  float lambda, sigma, maxnorm, weightDecay, gradnoise_eta, gradnoise_gamma;
+  unsigned long long gradnoise_seed, sample_seed;
+};
+size_t wnoise_state_bytes();
+int wnoise_state_reset(hipStream_t st, void* state);
+int wnoise_set_steps(hipStream_t st, void* state, unsigned t_sample, unsigned t_gradnoise);
+int wnoise_init(hipStream_t st, const WnoiseConfig& c, const float* params, float* weight, size_t n);
+int wnoise_sample(hipStream_t st, const WnoiseConfig& c, const float* weight, float* params, size_t n, void* state);
+int wnoise_backward(hipStream_t st, const WnoiseConfig& c, const float* weight, const float* params, float* grads,
+                    float* gradWeight, size_t n, const float* nll, int B, void* state, float* out,
+                    const unsigned* status, const float* skip_flag);
+int wnoise_mode(hipStream_t st, const float* weight, float* params, size_t n);
+
 }  // namespace s2s

@@ -90,6 +90,15 @@ int s2s_optim_adadelta_step(s2s_ctx* ctx, s2s_stream_t stream, const s2s_optim_c
 int s2s_ctx_status_flag(s2s_ctx* ctx, s2s_stream_t stream, float* flag);
 int s2s_optim_adadelta_step_flag(s2s_ctx* ctx, s2s_stream_t stream, const s2s_optim_config* cfg, float* params, float* grads, size_t n, void* state, const long* mats, int n_mats, float* gradnorm, const float* skip_flag);
 int s2s_model_weight_matrices(const s2s_model_dims* d, long* mats);
+typedef struct { int adaptive; float lambda, sigma; float maxnorm, weightDecay; float gradnoise_eta, gradnoise_gamma; unsigned long long gradnoise_seed; unsigned long long sample_seed; } s2s_wnoise_config;
+size_t s2s_wnoise_state_bytes(void);
+int s2s_wnoise_reset(s2s_ctx* ctx, s2s_stream_t stream, void* state);
+int s2s_wnoise_set_steps(s2s_ctx* ctx, s2s_stream_t stream, void* state, unsigned t_sample, unsigned t_gradnoise);
+int s2s_wnoise_init(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* params, float* weight, size_t n);
+int s2s_wnoise_sample(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* weight, float* params, size_t n, void* state);
+int s2s_wnoise_backward(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* weight, const float* params, float* grads, float* gradWeight, size_t n, const float* nll, int B, void* state, float* out);
+int s2s_wnoise_backward_flag(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* weight, const float* params, float* grads, float* gradWeight, size_t n, const float* nll, int B, void* state, float* out, const float* skip_flag);
+int s2s_wnoise_mode(s2s_ctx* ctx, s2s_stream_t stream, const s2s_wnoise_config* cfg, const float* weight, float* params, size_t n);
 int s2s_prof_enable(int on);
 int s2s_prof_collect(char* buf, size_t cap);
 int s2s_comm_unique_id(void* out_bytes);
@@ -329,6 +338,66 @@ function M.adadelta_step(ctx, stream, d, opt, params, grads, state, gradnorm, gr
    end
    M.check(C.s2s_optim_adadelta_step(ctx, stream, cfg, dptr(params), dptr(grads), n, vptr(state), M._mats,
                                      M._nmats, gradnorm and dptr(gradnorm) or nil))
+end
+
+-- nn.WeightNoise / nn.AdaptiveWeightNoise (WeightNoise.lua, AdaptiveWeightNoise.lua) and the trainer code around
+-- them (timit/timit.lua:190-205, 241-252, 291-333, 375-379) on the device.  wn is a table the caller keeps:
+--   wn = {adaptive = opt.adaweightnoise, lambda = opt.adalambda, sigma = opt.adasigmainit or opt.weightnoise,
+--         weight = CudaTensor, gradWeight = CudaTensor, state = CudaByteTensor, out = CudaTensor, seed = ...}
+-- weight / gradWeight are the module's (2n adaptive: [mu ; s] / [gradmu ; grads]; n fixed): hand them to
+-- M.adadelta_step in place of parameters / gradients, with opt.maxnorm / weightDecay and gradnoise left out
+-- there (wnoise_backward applies them).  One Sample() per call: call wnoise_sample once per minibatch.
+local function wnoise_cfg(wn, opt, gradnoise)
+   local cfg = ffi.new('s2s_wnoise_config')
+   cfg.adaptive = wn.adaptive and 1 or 0
+   cfg.lambda, cfg.sigma = wn.lambda or 1, wn.sigma or (wn.adaptive and 1 or 1e-3)
+   cfg.maxnorm, cfg.weightDecay = opt and opt.maxnorm or 1e20, opt and opt.weightDecay or 0
+   local gn = gradnoise or {eta = 0, gamma = 0.55}
+   cfg.gradnoise_eta, cfg.gradnoise_gamma = gn.eta or 0, gn.gamma or 0.55
+   cfg.gradnoise_seed, cfg.sample_seed = gn.seed or 0x5EED, wn.seed or 0x5A3D1E
+   return cfg
+end
+
+-- nn.WeightNoise(parameters, sigma) / nn.AdaptiveWeightNoise(parameters, lambda, sigma_init): sizes and fills
+-- wn.weight (mu <- parameters, s <- log(sigma_init^2)), wn.gradWeight, wn.state (counters 0) and wn.out
+function M.wnoise_init(ctx, stream, wn, params)
+   local n = params:nElement()
+   local m = wn.adaptive and 2 * n or n
+   wn.weight:resize(m)
+   wn.gradWeight:resize(m):zero()
+   wn.state:resize(tonumber(C.s2s_wnoise_state_bytes()))
+   wn.out:resize(6):zero()
+   wn.t = 0
+   M.check(C.s2s_wnoise_reset(ctx, stream, vptr(wn.state)))
+   M.check(C.s2s_wnoise_init(ctx, stream, wnoise_cfg(wn), dptr(params), dptr(wn.weight), n))
+end
+
+-- parameters:copy(Sample()) (timit.lua:241-252).  wn.t counts the samples drawn (the device counter, mirrored
+-- here so a checkpointed wn resumes the draw sequence: s2s_wnoise_set_steps in wnoise_backward / a resume)
+function M.wnoise_sample(ctx, stream, wn, params)
+   M.check(C.s2s_wnoise_sample(ctx, stream, wnoise_cfg(wn), dptr(wn.weight), dptr(params), params:nElement(),
+                               vptr(wn.state)))
+   wn.t = (wn.t or 0) + 1
+end
+
+-- timit.lua:297-333 after the model step: clip, L2 on the sampled parameters, gradient noise, then the module's
+-- forward(nll) + backward(nll, gradients).  nll: the step's (B) CudaTensor.  wn.out = {L, nll, KL, gradnorm,
+-- alpha_mu, alpha_sigma2} on the device; gradnoise as in M.adadelta_step (its t is set on the device before the
+-- call and advanced in the table, timit.lua:312).
+function M.wnoise_backward(ctx, stream, wn, opt, params, grads, nll, gradnoise)
+   local gn = gradnoise
+   if gn and (gn.eta or 0) ~= 0 then
+      M.check(C.s2s_wnoise_set_steps(ctx, stream, vptr(wn.state), wn.t or 0, gn.t or 0))
+      gn.t = (gn.t or 0) + 1
+   end
+   M.check(C.s2s_wnoise_backward(ctx, stream, wnoise_cfg(wn, opt, gn), dptr(wn.weight), dptr(params), dptr(grads),
+                                 dptr(wn.gradWeight), params:nElement(), dptr(nll), nll:nElement(), vptr(wn.state),
+                                 dptr(wn.out)))
+end
+
+-- parameters:copy(Mode()) before Evaluate (timit.lua:375-379)
+function M.wnoise_mode(ctx, stream, wn, params)
+   M.check(C.s2s_wnoise_mode(ctx, stream, wnoise_cfg(wn), dptr(wn.weight), dptr(params), params:nElement()))
 end
 
 -- nn.TemporalConvolution(Din, Dout, kW) on a (L x Din) or (B x L x Din) CudaTensor, as the conv + BiLSTM

@@ -36,6 +36,12 @@ class s2s_optim_config(ctypes.Structure):
                 ("gradnoise_seed", ctypes.c_ulonglong)]
 
 
+class s2s_wnoise_config(ctypes.Structure):
+    _fields_ = [("adaptive", c_int), ("lambda", c_float), ("sigma", c_float), ("maxnorm", c_float),
+                ("weightDecay", c_float), ("gradnoise_eta", c_float), ("gradnoise_gamma", c_float),
+                ("gradnoise_seed", ctypes.c_ulonglong), ("sample_seed", ctypes.c_ulonglong)]
+
+
 class s2s_model_dims(ctypes.Structure):
     _fields_ = [("B", c_int), ("L", c_int), ("T", c_int), ("inputFrameSize", c_int), ("hiddenFrameSize", c_int),
                 ("outputFrameSize", c_int), ("numLayers", c_int), ("scoreDepth", c_int), ("stateDepth", c_int),
@@ -121,6 +127,17 @@ SIGNATURES = [
     ("s2s_optim_adadelta_step_flag", c_int, [c_void_p, c_void_p, P(s2s_optim_config), c_void_p, c_void_p, c_size_t,
                                              c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     ("s2s_model_weight_matrices", c_int, [P(s2s_model_dims), c_void_p]),
+    ("s2s_wnoise_state_bytes", c_size_t, []),
+    ("s2s_wnoise_reset", c_int, [c_void_p, c_void_p, c_void_p]),
+    ("s2s_wnoise_set_steps", c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_uint, ctypes.c_uint]),
+    ("s2s_wnoise_init", c_int, [c_void_p, c_void_p, P(s2s_wnoise_config), c_void_p, c_void_p, c_size_t]),
+    ("s2s_wnoise_sample", c_int, [c_void_p, c_void_p, P(s2s_wnoise_config), c_void_p, c_void_p, c_size_t,
+                                  c_void_p]),
+    ("s2s_wnoise_backward", c_int, [c_void_p, c_void_p, P(s2s_wnoise_config), c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p]),
+    ("s2s_wnoise_backward_flag", c_int, [c_void_p, c_void_p, P(s2s_wnoise_config), c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    ("s2s_wnoise_mode", c_int, [c_void_p, c_void_p, P(s2s_wnoise_config), c_void_p, c_void_p, c_size_t]),
     ("s2s_model_bucket_count", c_int, [P(s2s_model_dims)]),
     ("s2s_model_bucket", c_int, [P(s2s_model_dims), c_int, P(c_size_t), P(c_size_t)]),
     ("s2s_stream_wait_bucket", c_int, [c_void_p, c_void_p, c_int]),

@@ -12,6 +12,14 @@ launch failed poisons every replica's sum -- all ranks must skip that update tog
     flag = opt.failure_flag()                   # 1.0 on a rank whose step failed (device, stream-ordered)
     dist.reduce_failure_flag(flag)              # MAX over the ranks
     opt.step(skip_flag=flag)                    # skipped on every rank if any rank failed
+
+Weight noise (WeightNoise.lua) and adaptive weight noise (AdaptiveWeightNoise.lua) as the reference trainer wires
+them (timit/timit.lua:190-205, 241-252, 291-333, 375-379), on the device (libs2s_hip.so: s2s_wnoise_*):
+
+    awn = AdaptiveWeightNoise(model, adalambda=1/B, sigma_init=0.075, maxnorm=1, ...)
+    opt = Adadelta(params=awn.weight, grads=awn.gradWeight, ctx=model.ctx)   # clip / L2 / noise belong to awn
+    awn.sample(); nll, _ = model.step(x, y); awn.backward(nll); opt.step()
+    awn.mode()   # before evaluation / beam search
 """
 import ctypes
 
@@ -98,3 +106,168 @@ class Adadelta:
         check(lib.s2s_optim_adadelta_step_flag(self.ctx.handle, st, ctypes.byref(self.cfg), dptr(self.params),
                                                dptr(self.grads), self.n, dptr(self.state), self._mats, self._nmats,
                                                dptr(self.gradnorm), dptr(skip_flag)))
+
+
+class _WeightNoiseBase:
+    """Shared host side of WeightNoise / AdaptiveWeightNoise: the trainable `weight` and its `gradWeight`, the
+    device state block (both counters, the clip / KL scalars) and the six-float device output of backward().
+    The trainer's clip (opt.maxnorm), L2 (opt.weightDecay, on the SAMPLED parameters) and gradient noise
+    (gradnoise = {eta, gamma}) are applied by backward() to the model gradient before the module sees it
+    (timit/timit.lua:297-315), so the optimizer on `weight` must leave them off.
+
+    Three deliberate differences from the reference:
+      1. One draw per sample() call.  The reference draws a new sample per utterance inside its per-utterance
+         loop (timit.lua:241-252); the step here is batched, so call sample() once per minibatch (the same
+         thing at B = 1).
+      2. Counter-based draws: element i of call t is noise_normal(key(sample_seed, t), i), the generator of the
+         gradient noise with a seed of its own, so every launch geometry and data-parallel rank draws the same
+         sample.  With both noises on, sample_seed must differ from gradnoise_seed (ValueError otherwise).
+      3. Column-norm constraint: Adadelta(params=weight, ..., mats=weight_matrices(cfg), colnormconstr=True)
+         constrains the rows of mu (the matrix offsets index the first n elements); the reference's constraint
+         lands on the sampled copy, which the next draw overwrites (timit.lua:344-346)."""
+
+    def __init__(self, adaptive, lam, sigma, model, params, grads, maxnorm, weightDecay, gradnoise_eta,
+                 gradnoise_gamma, gradnoise_seed, sample_seed, ctx):
+        if model is not None:
+            params, grads = model.getParameters()
+        if not (params.is_cuda and params.dtype == torch.float32 and params.is_contiguous() and params.dim() == 1
+                and grads.shape == params.shape and grads.dtype == torch.float32 and grads.is_contiguous()
+                and params.numel() > 0):
+            raise ValueError("params / grads must be flat contiguous float32 CUDA tensors of one size")
+        if gradnoise_eta != 0 and int(gradnoise_seed) == int(sample_seed):
+            raise ValueError("sample_seed must differ from gradnoise_seed when gradient noise is on: equal seeds "
+                             "and counters would draw the same normals for both")
+        self.params, self.grads = params, grads
+        self.n = params.numel()
+        self.adaptive = bool(adaptive)
+        self.cfg = _lib.s2s_wnoise_config(int(self.adaptive), lam, sigma, maxnorm, weightDecay, gradnoise_eta,
+                                          gradnoise_gamma, gradnoise_seed, sample_seed)
+        dev = params.device
+        m = 2 * self.n if self.adaptive else self.n
+        self.weight = torch.empty(m, dtype=torch.float32, device=dev)
+        self.gradWeight = torch.zeros(m, dtype=torch.float32, device=dev)
+        self.state = torch.zeros(lib.s2s_wnoise_state_bytes(), dtype=torch.uint8, device=dev)
+        self.out = torch.zeros(6, dtype=torch.float32, device=dev)
+        if ctx is None:
+            ctx = getattr(model, "ctx", None) or get_context(dev.index)
+        self.ctx = ctx
+        check(lib.s2s_wnoise_init(self.ctx.handle, stream_ptr(), ctypes.byref(self.cfg), dptr(params),
+                                  dptr(self.weight), self.n))
+
+    # device views of the last backward(): no host sync until the caller reads them
+    @property
+    def L(self):
+        """The loss the optimizer minimises: lambda * KL + nll (adaptive, lambda > 0), else nll (with the L2 term)."""
+        return self.out[0:1]
+
+    @property
+    def nll(self):
+        """Mean nll over the minibatch, plus 0.5 * weightDecay * ||parameters||^2 (timit.lua:292-308)."""
+        return self.out[1:2]
+
+    @property
+    def KL(self):
+        return self.out[2:3]
+
+    @property
+    def gradnorm(self):
+        """||g|| before clipping (timit.lua:297 gradnorms)."""
+        return self.out[3:4]
+
+    @property
+    def alpha_mu(self):
+        return self.out[4:5]
+
+    @property
+    def alpha_sigma2(self):
+        return self.out[5:6]
+
+    @staticmethod
+    def _st(stream):
+        return ctypes.c_void_p(stream.cuda_stream) if stream is not None else stream_ptr()
+
+    def sample(self, stream=None):
+        """parameters <- Sample() (AdaptiveWeightNoise.lua:27-38 / WeightNoise.lua:17-22): ONE draw, keyed on
+        (sample_seed, the device sample counter after its increment)."""
+        check(lib.s2s_wnoise_sample(self.ctx.handle, self._st(stream), ctypes.byref(self.cfg), dptr(self.weight),
+                                    dptr(self.params), self.n, dptr(self.state)))
+
+    def backward(self, nll, skip_flag=None, stream=None):
+        """After model.step (params still hold the sample; nll = its (B,) device losses): clip, L2, gradient noise
+        on grads in place, then the module's updateOutput + accGradParameters into gradWeight (timit.lua:297-333).
+        skip_flag as in Adadelta.step: nonzero (or the context's failure status set) when this runs on the device
+        leaves grads, gradWeight and both counters untouched; gradnorm is still written."""
+        if not (nll.is_cuda and nll.dtype == torch.float32 and nll.is_contiguous() and nll.numel() >= 1):
+            raise ValueError("nll must be a contiguous float32 CUDA tensor of the minibatch's losses")
+        args = (self.ctx.handle, self._st(stream), ctypes.byref(self.cfg), dptr(self.weight), dptr(self.params),
+                dptr(self.grads), dptr(self.gradWeight), self.n, dptr(nll), nll.numel(), dptr(self.state),
+                dptr(self.out))
+        if skip_flag is None:
+            check(lib.s2s_wnoise_backward(*args))
+            return
+        if not (skip_flag.is_cuda and skip_flag.dtype == torch.float32 and skip_flag.numel() >= 1):
+            raise ValueError("skip_flag must be a float32 CUDA tensor")
+        check(lib.s2s_wnoise_backward_flag(*args, dptr(skip_flag)))
+
+    def mode(self, stream=None):
+        """parameters <- Mode() (mu / weight) before evaluation or beam search (timit.lua:375-379)."""
+        check(lib.s2s_wnoise_mode(self.ctx.handle, self._st(stream), ctypes.byref(self.cfg), dptr(self.weight),
+                                  dptr(self.params), self.n))
+
+    def set_steps(self, t_sample, t_gradnoise, stream=None):
+        """Counters of a resumed run: the next sample() draws with t_sample + 1, the next noised backward() with
+        t_gradnoise + 1 (gradnoise.t, timit.lua:92, 312)."""
+        check(lib.s2s_wnoise_set_steps(self.ctx.handle, self._st(stream), dptr(self.state), int(t_sample),
+                                       int(t_gradnoise)))
+
+    def steps(self):
+        """(t_sample, t_gradnoise) read back from the device (synchronises)."""
+        t = self.state[:8].view(torch.int32).cpu()
+        return int(t[0]) & 0xFFFFFFFF, int(t[1]) & 0xFFFFFFFF
+
+    def state_dict(self):
+        t_s, t_g = self.steps()
+        return {"weight": self.weight.detach().clone(), "t_sample": t_s, "t_gradnoise": t_g,
+                "sample_seed": int(self.cfg.sample_seed), "gradnoise_seed": int(self.cfg.gradnoise_seed)}
+
+    def load_state_dict(self, sd):
+        if sd["weight"].numel() != self.weight.numel():
+            raise ValueError("state_dict's weight has another size (adaptive vs fixed, or another model)")
+        self.weight.copy_(sd["weight"])
+        self.cfg.sample_seed, self.cfg.gradnoise_seed = int(sd["sample_seed"]), int(sd["gradnoise_seed"])
+        self.set_steps(sd["t_sample"], sd["t_gradnoise"])
+
+
+class WeightNoise(_WeightNoiseBase):
+    """nn.WeightNoise(parameters, sigma) (WeightNoise.lua; opt.weightnoise, timit.lua:190-195): weight (n) starts
+    as the parameters, sample() sets parameters = weight + sigma * N(0, 1), backward() leaves gradWeight = the
+    clipped / decayed / noised gradient and L = nll, mode() restores parameters = weight.  See _WeightNoiseBase
+    for the loop and the three differences from the reference."""
+
+    def __init__(self, model=None, sigma=1e-3, params=None, grads=None, maxnorm=1e20, weightDecay=0.0,
+                 gradnoise_eta=0.0, gradnoise_gamma=0.55, gradnoise_seed=0x5EED, sample_seed=0x5A3D1E, ctx=None):
+        super().__init__(False, 0.0, sigma, model, params, grads, maxnorm, weightDecay, gradnoise_eta,
+                         gradnoise_gamma, gradnoise_seed, sample_seed, ctx)
+
+
+class AdaptiveWeightNoise(_WeightNoiseBase):
+    """nn.AdaptiveWeightNoise(parameters, lambda, sigma_init) (AdaptiveWeightNoise.lua; opt.adaweightnoise,
+    opt.adalambda = 1/B, opt.adasigmainit, timit.lua:196-205): weight = [mu ; s] (2n), s = log sigma^2, starting
+    at mu = parameters, s = log(sigma_init^2).  sample() sets parameters = mu + exp(s)^0.5 * N(0, 1);
+    backward() computes alpha_mu, alpha_sigma2, KL and L = adalambda * KL + nll (:63-80) and gradWeight =
+    [gradmu ; grads] (:82-104); mode() restores parameters = mu.  The sums behind alpha_* and KL are taken in
+    double in a fixed order.  See _WeightNoiseBase for the loop and the three differences from the reference."""
+
+    def __init__(self, model=None, adalambda=1.0, sigma_init=1.0, params=None, grads=None, maxnorm=1e20,
+                 weightDecay=0.0, gradnoise_eta=0.0, gradnoise_gamma=0.55, gradnoise_seed=0x5EED,
+                 sample_seed=0x5A3D1E, ctx=None):
+        super().__init__(True, adalambda, sigma_init, model, params, grads, maxnorm, weightDecay, gradnoise_eta,
+                         gradnoise_gamma, gradnoise_seed, sample_seed, ctx)
+
+    @property
+    def mu(self):
+        return self.weight[:self.n]
+
+    @property
+    def s(self):
+        return self.weight[self.n:]
