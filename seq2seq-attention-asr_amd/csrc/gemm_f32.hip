@@ -700,6 +700,8 @@ void set_gemm_precision(int p) { g_gemm_prec = p; }
 int gemm_precision() { return g_gemm_prec; }
 void set_wgrad_bf16(bool on) { g_wgrad_bf16 = on; }
 bool wgrad_bf16() { return g_wgrad_bf16; }
+static thread_local GemmLastPlan g_last_plan;
+const GemmLastPlan& gemm_last_plan() { return g_last_plan; }
 
 struct GemmPlan {
   int bm = 64, bn = 64, kslice = 0, nblocks = 0;
@@ -800,13 +802,17 @@ static void launch_tiles(hipStream_t st, const GemmPlan& pl, dim3 grid, const Ge
 }
 
 int gemm_f32(hipStream_t st, const GemmProblem* probs, int nprob, bool transA, bool transB, GemmWs ws) {
+  GemmLastPlan& rec = g_last_plan;
+  rec = GemmLastPlan{};
   S2S_REQUIRE(nprob >= 1 && nprob <= kMaxGemmBatch, "gemm_f32: bad batch count");
   GemmProblem use[kMaxGemmBatch];
+  int src[kMaxGemmBatch];  // the caller's index of use[i]
   int used = 0;
   for (int i = 0; i < nprob; ++i) {
     const GemmProblem& q = probs[i];
     if (q.M <= 0 || q.N <= 0) continue;
     S2S_REQUIRE(q.K >= 0 && q.C != nullptr, "gemm_f32: bad problem");
+    src[used] = i;
     use[used++] = q;
   }
   if (used == 0) return 0;
@@ -820,7 +826,10 @@ int gemm_f32(hipStream_t st, const GemmProblem* probs, int nprob, bool transA, b
       const GemmProblem& q = use[i];
       bool done = false;
       if (2.0 * q.M * (double)q.N * q.K >= 1e9) S2S_TRY(gemm_big_bf16(st, q, transA, transB, &done));
-      if (!done) use[keep++] = q;
+      if (!done) {
+        src[keep] = src[i];
+        use[keep++] = q;
+      }
     }
     used = keep;
     if (used == 0) return 0;
@@ -846,12 +855,18 @@ int gemm_f32(hipStream_t st, const GemmProblem* probs, int nprob, bool transA, b
       woff += (size_t)t.splits * t.p.M * t.p.N;
       split = true;
     }
+    rec.splits[src[i]] = t.splits;
     t.base = base;
     base += t.tiles_m * t.tiles_n * t.splits;
     flops += 2.0 * t.p.M * t.p.N * t.p.K;
     bytes += 4.0 * ((double)t.p.M * t.p.K + (double)t.p.K * t.p.N + (double)t.p.M * t.p.N * (t.p.beta != 0.f ? 2 : 1));
   }
   L.nblocks = base;
+  rec.bm = pl.bm;
+  rec.bn = pl.bn;
+  rec.kslice = pl.kslice;
+  rec.nblocks = base;
+  rec.launched = 1;
   ProfScope ps(st, bf16 ? "gemm_bf16" : "gemm_f32", flops, bytes);
   const dim3 grid((unsigned)((base + 7) / 8 * 8));
   if (!transA && !transB) launch_tiles<false, false>(st, pl, grid, L, bf16);
@@ -870,6 +885,7 @@ int gemm_f32(hipStream_t st, const GemmProblem* probs, int nprob, bool transA, b
       if (L.q[i].part) mn_max = std::max(mn_max, (long)L.q[i].p.M * L.q[i].p.N);
     const unsigned gx = (unsigned)std::min<long>(1024, (mn_max + 1023) / 1024);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(gx, used), dim3(256), 0, st, L);
+    rec.reduced = 1;
   }
   S2S_CHECK_HIP(hipGetLastError());
   return 0;
@@ -896,6 +912,10 @@ int colsum_scatter_f32(hipStream_t st, const float* X, long ldx, int M, int N, f
                        int nouts, GemmWs ws) {
   S2S_REQUIRE(nouts >= 0 && nouts <= kMaxColsumOuts, "colsum_scatter: too many output ranges");
   if (N <= 0 || nouts == 0) return 0;
+  for (int e = 0; e < nouts; ++e)  // before either form: the one-stage form indexes dst[q] too
+    S2S_REQUIRE(outs[e].col0 >= 0 && outs[e].ncols >= 0 && outs[e].col0 + outs[e].ncols <= N && outs[e].ndst >= 0 &&
+                    outs[e].ndst <= 3,
+                "colsum_scatter: bad range");
   const int parts = colsum_parts(M);
   if (!(ws.p && parts > 1 && ws.n >= (size_t)kColParts * N)) {  // colsum_f32's one-stage form per destination
     for (int e = 0; e < nouts; ++e)
@@ -906,7 +926,6 @@ int colsum_scatter_f32(hipStream_t st, const float* X, long ldx, int M, int N, f
   ColsumOuts o{};
   int maxc = 0;
   for (int e = 0; e < nouts; ++e) {
-    S2S_REQUIRE(outs[e].col0 >= 0 && outs[e].col0 + outs[e].ncols <= N && outs[e].ndst <= 3, "colsum_scatter: bad range");
     o.e[e] = outs[e];
     maxc = std::max(maxc, outs[e].ncols);
   }

@@ -179,6 +179,15 @@ struct GemmWs {
 constexpr size_t kGemmWsFloats = size_t(8) << 20;  // 32 MiB
 // All problems of one call share transA/transB.
 int gemm_f32(hipStream_t st, const GemmProblem* probs, int nprob, bool transA, bool transB, GemmWs ws = GemmWs{});
+// What the calling thread's last gemm_f32 call launched, written by that call from the values it launched with (the
+// tests of the split-K paths assert it: s2s_debug_gemm_batch): the tile shape, the K slice and the logical blocks of
+// the tile kernel, and per problem of the call, in the caller's order, its slice count (0: skipped, M or N <= 0).
+// launched = 0: the call returned before the tile kernel (nothing to do, an error, or the big bf16 GEMM took it all).
+struct GemmLastPlan {
+  int launched = 0, bm = 0, bn = 0, kslice = 0, nblocks = 0, reduced = 0;
+  int splits[kMaxGemmBatch] = {};
+};
+const GemmLastPlan& gemm_last_plan();
 // staging buffers for the big bf16 GEMMs' operand copies, owned by a context (grown outside stream capture
 // only): one per stream, so calls the caller issues on different streams never share bytes (a buffer is
 // reused only in its own stream's order)
