@@ -10,7 +10,7 @@
 
 namespace s2s {
 
-// test knob (s2s_debug_inject_abort, capi.cpp): 1 when this sync_prep starts its region aborted
+// test knob (s2s_debug_inject_abort, capi_debug.cpp): 1 when this sync_prep starts its region aborted
 int inject_abort_take();
 
 // ---------------------------------------------------------------- errors

@@ -152,7 +152,7 @@ def reference(c, dtype, kslice=0, opA=None, opB=None):
 
 
 def declare(lib):
-    """ctypes signatures of the test entry points of csrc/capi.cpp (s2s_debug_gemm_batch and the helpers' entries);
+    """ctypes signatures of the test entry points of csrc/capi_debug.cpp (s2s_debug_gemm_batch and the helpers' entries);
     -> a namespace with the argument structs Problem, Plan and ColsumOut."""
     import ctypes as ct
     vp, i, f, lg, sz = ct.c_void_p, ct.c_int, ct.c_float, ct.c_long, ct.c_size_t

@@ -80,6 +80,37 @@ def test_chorowski_param_count():
     assert n + 513 == 4356735
 
 
+def test_layout_check_under_host_sanitizers(tmp_path):
+    """csrc/layout_check.cpp (the flat layout's one table, model_layout.cpp, as a stand-alone host program under
+    ASan + UBSan: no HIP, no GPU) passes its walk of valid, degenerate and invalid models, and the table it prints
+    for the default model is the Python layout's and the loaded library's: the same source compiled twice agrees."""
+    import subprocess
+    from s2s_amd import _lib, model
+    exe = tmp_path / "layout_check"
+    r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "seq2seq-attention-asr_amd", "csrc"), "layout_check",
+                        f"LAYOUT_CHECK={exe}"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr
+    table = [tuple(int(v) for v in line.split()) for line in r.stdout.splitlines()]
+    cfg = model.ModelConfig()
+    shapes = model.param_shapes(cfg)
+    assert [t[0] for t in table] == list(range(len(shapes)))
+    d = _lib.s2s_model_dims(32, 128, 40, cfg.inputFrameSize, cfg.hiddenFrameSize, cfg.outputFrameSize,
+                            cfg.numLayers, cfg.scoreDepth, cfg.stateDepth, cfg.outputDepth, cfg.mlpDepth,
+                            cfg.maxoutWindow, cfg.penalty)
+    off = 0
+    for (i, o, n, rows, cols), (_, shp) in zip(table, shapes):
+        assert (o, n) == (off, math.prod(shp)), i
+        assert (rows, cols) == (shp if len(shp) == 2 else (0, shp[0])), i
+        numel = ctypes.c_long(-1)
+        assert _lib.lib.s2s_model_param_offset(ctypes.byref(d), i, ctypes.byref(numel)) == o, i
+        assert numel.value == n, i
+        off += n
+    assert off == 4356222 == 4356735 - 513
+    assert _lib.lib.s2s_model_param_count(ctypes.byref(d)) == off
+    assert _lib.lib.s2s_model_param_offset(ctypes.byref(d), len(table), None) == -1
+
+
 def test_errors_are_reported_not_aborted():
     from s2s_amd import _lib
     d = _lib.s2s_model_dims(0, 8, 3, 123, 256, 256, 3, 512, 256, 62, 64, 7, 0.0)

@@ -1,5 +1,5 @@
 """GPU: the fp32 MFMA GEMM and its helpers (csrc/gemm_f32.hip) tested directly, against float64, through the test
-entry points of csrc/capi.cpp (s2s_debug_gemm_batch and one entry per helper).
+entry points of csrc/capi_debug.cpp (s2s_debug_gemm_batch and one entry per helper).
 
 The cases come from tests/gemm_case.py: operands and outputs are windows at odd offsets with odd leading dimensions
 inside NaN-filled (inputs) or canary-filled (outputs) arrays, and the data is exact -- small non-zero integers, so

@@ -1,4 +1,4 @@
-# A/B of the decoder-fold placement (S2S_PROLOGUE, capi.cpp model_step_impl) on one GPU:
+# A/B of the decoder-fold placement (S2S_PROLOGUE, model_step.cpp model_step_impl) on one GPU:
 #   tools/ab_prologue.sh [OUTDIR]  ->  OUTDIR/ab_<mode>.json (default: ab_out/)
 set -e
 out=${1:-ab_out}
