@@ -873,15 +873,16 @@ def decoder_zero_state(L: int, S: int, dtype=np.float64):
 
 
 def beam_search(h: Array, P: Dict[str, Array], cfg: "ModelConfig", eos: int, K: int = 5,
-                maxseqlength: Optional[int] = None, mlp=None):
+                maxseqlength: Optional[int] = None, mlp=None, finished=None):
     """Attention:BeamSearch (Attention.lua:332-438) for one utterance h (L, A), 0-based labels.
     Step 0 from zeros_y / zero hidden (:356-367), torch.topk(K) sorted (:369); then while fewer
     than K hypotheses finished and count < maxseqlength (:384): every active hypothesis k is
     extended (p_next[k] = logp + p_beam[k], :386-399), topk(K) over the flattened candidates
     (:400-402), of which the first K - finished are taken (:408): eos or count == maxseqlength
     finishes (:413-417), else it survives with its parent's hidden {alpha, s, mem}.  mlp: an external
-    decoder_mlp (decoder_step).  Returns (prediction = the finished hypothesis of highest score
-    (first maximum, :432-434), score)."""
+    decoder_mlp (decoder_step).  finished: a list that receives every finished (sequence, score) in
+    finishing order (y_finished / p_finished, :375-376).  Returns (prediction = the finished hypothesis of
+    highest score (first maximum, :432-434), score)."""
     L = h.shape[0]
     maxlen = maxseqlength or L
     Vh = h @ P["V"].T
@@ -912,6 +913,8 @@ def beam_search(h: Array, P: Dict[str, Array], cfg: "ModelConfig", eos: int, K: 
             else:
                 new_beams.append((seq, nexts[i][1], float(flat[idx])))
         beams = new_beams
+    if finished is not None:
+        finished.extend(fin)
     best = int(np.argmax([f[1] for f in fin]))
     return fin[best][0], fin[best][1]
 

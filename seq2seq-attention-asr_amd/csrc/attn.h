@@ -128,6 +128,9 @@ int attn_beam_advance(hipStream_t st, const AttnDims& d, int eos, int K, int max
 int attn_beam_done(hipStream_t st, const AttnDims& d, int K, int maxlen, void* ws, int* all_done);
 int attn_beam_finish(hipStream_t st, const AttnDims& d, int K, int maxlen, void* ws, int* out, int ldo, int* out_len,
                      float* out_score);
+// diagnostic (s2s_debug_beam_finished): nfin (B), flen (B*K), fscore (B*K), fseq (B*K*(maxlen+1)) of the search
+int attn_beam_finished(hipStream_t st, const AttnDims& d, int K, int maxlen, void* ws, int* nfin, int* flen,
+                       float* fscore, int* fseq);
 // WagnerFischer (utils.lua:3-27) over n sequence pairs (row-major, lengths alen / blen)
 int edit_distance(hipStream_t st, int n, const int* a, const int* alen, int lda, const int* b, const int* blen,
                   int ldb, int* out);

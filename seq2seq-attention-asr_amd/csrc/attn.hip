@@ -2437,6 +2437,21 @@ int attn_beam_finish(hipStream_t st, const AttnDims& d, int K, int maxlen, void*
   return 0;
 }
 
+// diagnostic: every finished hypothesis of the search, the reference's y_finished / p_finished
+// (Attention.lua:375-376), copied device to device in stream order; entries at or beyond nfin[b] are unspecified
+int attn_beam_finished(hipStream_t st, const AttnDims& d, int K, int maxlen, void* ws, int* nfin, int* flen,
+                       float* fscore, int* fseq) {
+  BeamView v;
+  AttnParams P{};
+  S2S_TRY(beam_view(d, P, 0, K, maxlen, ws, beam_layout(d, K, maxlen).total, v));
+  const size_t R = (size_t)d.B * K, L1 = (size_t)maxlen + 1;
+  S2S_CHECK_HIP(hipMemcpyAsync(nfin, v.q.nfin, sizeof(int) * d.B, hipMemcpyDeviceToDevice, st));
+  S2S_CHECK_HIP(hipMemcpyAsync(flen, v.q.flen, sizeof(int) * R, hipMemcpyDeviceToDevice, st));
+  S2S_CHECK_HIP(hipMemcpyAsync(fscore, v.q.fscore, sizeof(float) * R, hipMemcpyDeviceToDevice, st));
+  S2S_CHECK_HIP(hipMemcpyAsync(fseq, v.q.fseq, sizeof(int) * R * L1, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
 int attn_beam_search(hipStream_t st, const AttnDims& d, const float* h, const AttnParams& P, int eos, int K,
                      int maxlen, int* out, int ldo, int* out_len, float* out_score, void* ws, size_t ws_bytes) {
   S2S_REQUIRE(!d.ext, "beam search: an external decoder_mlp runs through the stepwise calls");

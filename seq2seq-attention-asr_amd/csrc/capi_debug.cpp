@@ -116,6 +116,17 @@ extern "C" int s2s_debug_gemm_big_run(s2s_ctx* ctx, s2s_stream_t stream, int tra
   *done = d ? 1 : 0;
   return rc;
 }
+// diagnostic: every finished hypothesis of a beam search still in its workspace (the reference's y_finished /
+// p_finished, Attention.lua:375-376): nfin (B), flen (B*K), fscore (B*K), fseq (B*K*(maxseqlength+1)) device
+// buffers, filled in stream order; entries at or beyond nfin[b] are unspecified (tests/test_gpu_decode.py)
+extern "C" int s2s_debug_beam_finished(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, int K,
+                                       int maxseqlength, void* workspace, int* nfin, int* flen, float* fscore,
+                                       int* fseq) {
+  S2S_TRY(set_device(ctx));
+  S2S_REQUIRE(d && workspace && nfin && flen && fscore && fseq, "beam search: null argument");
+  return attn_beam_finished(static_cast<hipStream_t>(stream), to_attn(d), K, maxseqlength, workspace, nfin, flen,
+                            fscore, fseq);
+}
 // diagnostic: the context's 16 status words ([0] timeout, [1] aborted region, [4 + i] raw failure bits of the
 // last harvest's region i) -- tools/status_diag.py
 extern "C" int s2s_debug_status_words(s2s_ctx* ctx, unsigned* out16) {

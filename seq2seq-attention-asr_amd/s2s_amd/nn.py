@@ -698,13 +698,15 @@ class Attention(Module):
     def accGradParameters(self, input, gradOutput, scale=1.0):
         pass
 
-    def BeamSearch(self, annotations, eos, K=5, maxseqlength=None):
+    def BeamSearch(self, annotations, eos, K=5, maxseqlength=None, finished=False):
         """decoder:BeamSearch(annotations, eos, K, maxseqlength) (Attention.lua:332-438) in evaluate()
         mode.  annotations (L, A) -> 1-D int tensor (the prediction, 0-based tokens, eos last when it
         finished on eos); (B, L, A) -> (tokens (B, maxseqlength + 1) padded with -1, lengths (B),
         scores (B)).  maxseqlength defaults to L (:337).  Content or hybrid attention, GRU or LSTM
         decoder_recurrent; an external decoder_mlp runs between the search's step and advance calls on
-        the (B*K, S+A) hypothesis rows."""
+        the (B*K, S+A) hypothesis rows.  finished=True (a diagnostic) also returns every finished hypothesis,
+        the reference's y_finished / p_finished (:375-376), in finishing order: (nfin (B), flen (B, K),
+        fscore (B, K), fseq (B, K, maxseqlength + 1)); entries at or beyond nfin[b] are unspecified."""
         h = annotations
         if h.dim() not in (2, 3):
             raise S2SArgumentError("annotations must be 2d or 3d")
@@ -760,9 +762,21 @@ class Attention(Module):
             finally:
                 if mlp_train is not None:
                     self.decoder_mlp.train = mlp_train
+        fin = ()
+        if finished:
+            K = int(K)
+            nfin = torch.empty(B, dtype=torch.int32, device=dev)
+            flen = torch.empty((B, K), dtype=torch.int32, device=dev)
+            fscore = torch.empty((B, K), dtype=torch.float32, device=dev)
+            fseq = torch.empty((B, K, maxlen + 1), dtype=torch.int32, device=dev)
+            fn = lib.s2s_debug_beam_finished  # a debug symbol: not in include/s2s_hip.h
+            fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 5
+            check(fn(ctx, st, ctypes.byref(d), K, maxlen, dptr(ws), dptr(nfin), dptr(flen), dptr(fscore), dptr(fseq)))
+            fin = (nfin, flen, fscore, fseq)
         if single:
-            return out[0, :int(olen[0].item())]
-        return out, olen, osc
+            pred = out[0, :int(olen[0].item())]
+            return (pred,) + fin if finished else pred
+        return (out, olen, osc) + fin
 
     def mono_ind(self):
         """(B, T) MonotonicAlignment indicators 1[penalty_t > 0] of the last forward

@@ -199,6 +199,9 @@ ATT_CASES = [
     # shapes served by the persistent decoder kernels (S=64, A=128, Sc=128), ragged B and L
     (5, 37, 6, 128, 128, 64, 29, 4, 7, 0.3),
     (18, 16, 4, 128, 128, 64, 62, 8, 7, 0.0),
+    # vocabularies wider than one wave: the MLP head's and the LogSoftMax's stride over outputDepth
+    (3, 20, 5, 32, 48, 32, 100, 4, 3, 0.0),
+    (5, 9, 4, 32, 48, 32, 65, 4, 3, 0.0),
 ]
 
 
@@ -217,6 +220,9 @@ XCD_CASES = [
     # edge shapes: one utterance of one frame and one label; one label per utterance, ragged chain
     (1, 1, 1, 128, 128, 64, 11, 4, 3, 0.0),
     (9, 3, 1, 512, 512, 256, 62, 8, 7, 0.0),
+    # vocabularies wider than one wave
+    (3, 20, 5, 128, 128, 64, 100, 4, 3, 0.0),
+    (5, 9, 4, 128, 128, 64, 65, 4, 3, 0.0),
 ]
 
 
