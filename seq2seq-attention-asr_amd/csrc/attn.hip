@@ -24,6 +24,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "decisions.h"
 #include "handoff.h"
 #include "skinny.h"
 
@@ -1398,8 +1399,9 @@ const float* attn_saved_dropout_mask(const AttnDims& d, const void* saved) {
   return k.MASK;
 }
 
-// S2S_DEC_MODE=step forces the per-step launch path (A/B and fallback); default: the persistent
-// decoder kernels whenever the shape has an instantiation.
+// The 7-seam persistent decoder kernels (attn_persist.inc): auto mode's fall-back where dec_xcd_plan declines a shape
+// of the instantiated widths (B > 128, a chunk longer than 64 frames, T > 256), or forced by dec_mode() = 2;
+// dec_mode() = 1 forces the per-step launches.
 static std::atomic<unsigned long long*> g_dec_stamps[2] = {{nullptr}, {nullptr}};
 
 static int dec_persist_variant(const AttnDims& d) {
@@ -1444,16 +1446,17 @@ static bool dec_res_enabled(const AttnDims& d) {
 struct PersistLaunch {
   const void* fn = nullptr;
   size_t lds = 0;
+  int res = -1;  // 1: the resident-chunk candidate, 0: the other one (the decision record's dec.persist_res)
 };
 
 static PersistLaunch pick_dec_fwd(int var, const AttnDims& d, int grid) {
   PersistLaunch c[2];
   if (var == 1) {
-    c[0] = {(const void*)dec_fwd_persist<4, 8, 2, true>, dec_fwd_res_lds(d.A, d.Sc)};
-    c[1] = {(const void*)dec_fwd_persist<4, 8, 2, false>, 0};
+    c[0] = {(const void*)dec_fwd_persist<4, 8, 2, true>, dec_fwd_res_lds(d.A, d.Sc), 1};
+    c[1] = {(const void*)dec_fwd_persist<4, 8, 2, false>, 0, 0};
   } else {
-    c[0] = {(const void*)dec_fwd_persist<1, 2, 1, true>, dec_fwd_res_lds(d.A, d.Sc)};
-    c[1] = {(const void*)dec_fwd_persist<1, 2, 1, false>, 0};
+    c[0] = {(const void*)dec_fwd_persist<1, 2, 1, true>, dec_fwd_res_lds(d.A, d.Sc), 1};
+    c[1] = {(const void*)dec_fwd_persist<1, 2, 1, false>, 0, 0};
   }
   for (int i = dec_res_enabled(d) ? 0 : 1; i < 2; ++i)
     if (co_resident(c[i].fn, grid, c[i].lds)) return c[i];
@@ -1463,11 +1466,11 @@ static PersistLaunch pick_dec_fwd(int var, const AttnDims& d, int grid) {
 static PersistLaunch pick_dec_bwd(int var, const AttnDims& d, int grid) {
   PersistLaunch c[2];
   if (var == 1) {
-    c[0] = {(const void*)dec_bwd_persist<4, 8, true>, dec_bwd_res_lds(d.A, d.Sc)};
-    c[1] = {(const void*)dec_bwd_persist<4, 8, false>, 0};
+    c[0] = {(const void*)dec_bwd_persist<4, 8, true>, dec_bwd_res_lds(d.A, d.Sc), 1};
+    c[1] = {(const void*)dec_bwd_persist<4, 8, false>, 0, 0};
   } else {
-    c[0] = {(const void*)dec_bwd_persist<1, 2, true>, dec_bwd_res_lds(d.A, d.Sc)};
-    c[1] = {(const void*)dec_bwd_persist<1, 2, false>, 0};
+    c[0] = {(const void*)dec_bwd_persist<1, 2, true>, dec_bwd_res_lds(d.A, d.Sc), 1};
+    c[1] = {(const void*)dec_bwd_persist<1, 2, false>, 0, 0};
   }
   for (int i = dec_res_enabled(d) ? 0 : 1; i < 2; ++i)
     if (co_resident(c[i].fn, grid, c[i].lds)) return c[i];
@@ -1479,6 +1482,22 @@ static int launch_persist(const PersistLaunch& p, int grid, hipStream_t st, Attn
   S2S_TRY(check_resident(p.fn, grid, 256, p.lds, "decoder persistent launch"));
   S2S_CHECK_HIP(hipLaunchKernel(p.fn, dim3(grid), dim3(256), args, p.lds, st));
   return 0;
+}
+
+// The decision record (decisions.h) of one decoder launch, from the variables attn_fwd / attn_bwd_core steer it with:
+// path 0 steps, 1 persist, 2 xcd, 3 xcd_lstm; the XCD-local plan as handed to the kernel (0 on the other paths);
+// persist_res: which of pick_dec_fwd's / pick_dec_bwd's candidates was launched (-1: none).
+static void record_dec_launch(bool fwd, int path, const XPlan& xp, const XArgs& x, int persist_res) {
+  decide(fwd ? "dec.fwd.path" : "dec.bwd.path", path);
+  const bool xcd = path >= 2;
+  decide("dec.var", xcd ? xp.var : 0);
+  decide("dec.U", xcd ? x.U : 0);
+  decide("dec.nchains", xcd ? x.nchains : 0);
+  decide("dec.XLC", xcd ? x.XLC : 0);
+  decide("dec.NCH", xcd ? x.NCH : 0);
+  decide("dec.res", xcd ? xp.res : -1);
+  decide("dec.allow_local", xcd ? x.allow_local : 0);
+  decide("dec.persist_res", persist_res);
 }
 
 static std::atomic<int> g_dec_allow_local{1};
@@ -1498,6 +1517,7 @@ static bool attn_head_bwd_fused(const AttnDims& d) {
 
 // s2s_debug_dec_r4(0) (A/B): chains of <= 4 utterances keep the 16 x 16 x 4 skinny products
 static std::atomic<int> g_dec_r4{1};
+static std::atomic<int> g_dec_pf_host{1};  // what s2s_debug_dec_pf last wrote to the device's g_dec_pf (decision record)
 template <int S, int A, int SC, bool R4>
 static const void* xcd_kernel(bool fwd, int res) {
   return res == 2 ? (fwd ? (const void*)dec_xcd_fwd<S, A, SC, 2, R4> : (const void*)dec_xcd_bwd<S, A, SC, 2, R4>)
@@ -1508,7 +1528,10 @@ template <int S, int A, int SC>
 static int launch_xcd_t(bool fwd, int res, hipStream_t st, AttnK& k, XArgs& x) {
   const size_t lds = xdec_lds<S, A, SC>(x.XLC, res);
   // a chain of at most 4 utterances (B <= 32): its skinny products on the 4 x 4 x 1 MFMA (handoff.h mfma4_aw_acc)
-  const void* fn = x.U <= 4 && g_dec_r4.load() ? xcd_kernel<S, A, SC, true>(fwd, res) : xcd_kernel<S, A, SC, false>(fwd, res);
+  const bool r4 = x.U <= 4 && g_dec_r4.load();
+  const void* fn = r4 ? xcd_kernel<S, A, SC, true>(fwd, res) : xcd_kernel<S, A, SC, false>(fwd, res);
+  decide("dec.r4", r4);
+  decide("dec.pf", g_dec_pf_host.load());
   if (lds) S2S_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   void* args[] = {&k, &x};
   S2S_TRY(check_resident(fn, chain_grid(x.nchains, kXWG), 256, lds, fwd ? "dec_xcd_fwd" : "dec_xcd_bwd"));
@@ -1526,6 +1549,7 @@ static int launch_xcd_lstm(bool fwd, hipStream_t st, AttnK& k, XArgs& x, XLArgs&
                        : (const void*)dec_xcd_lstm_bwd<kXlSP, 256, 160, kXlSCP, 5, true>;
   if (lds) S2S_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   void* args[] = {&k, &x, &y};
+  decide("dec.r4", 1);
   S2S_TRY(check_resident(fn, chain_grid(x.nchains, kXWG), 256, lds, fwd ? "dec_xcd_lstm_fwd" : "dec_xcd_lstm_bwd"));
   S2S_CHECK_HIP(hipLaunchKernel(fn, dim3(chain_grid(x.nchains, kXWG)), dim3(256), args, lds, st));
   return 0;
@@ -1656,6 +1680,7 @@ int attn_fwd(hipStream_t st, const AttnDims& d, const float* h, const int* label
       // per forward; flops = the step products + the attention contractions
       ProfScope ps(st, xp.var == 3 ? "dec_fwd_xcd_lstm" : "dec_fwd_xcd", dec_flops(d, false),
                    4.0 * d.T * d.B * d.L * (double)(d.Sc + d.A));
+      record_dec_launch(true, xp.var == 3 ? 3 : 2, xp, x, -1);
       S2S_TRY(xp.var == 3 ? launch_xcd_lstm(true, st, k, x, y) : launch_xcd(xp, true, st, k, x));
     }
     // alpha / MonotonicAlignment indicators from the saved scores and VBAR (the backward's dws reference
@@ -1677,12 +1702,17 @@ int attn_fwd(hipStream_t st, const AttnDims& d, const float* h, const int* label
     S2S_TRY(launch_sync_prep(st, k.fsync, k.fsync_bytes, nullptr, k.fhdr));
     {
       ProfScope ps(st, "dec_fwd_persist", 0.0, 0.0);
+      record_dec_launch(true, 1, xp, x, pf.res);
       S2S_TRY(launch_persist(pf, pgrid, st, k));
     }
     hipLaunchKernelGGL(dec_alpha_ind, dim3(T, B), dim3(256), 0, st, k);
     S2S_CHECK_HIP(hipGetLastError());
   } else {
   ProfScope ps(st, "dec_fwd_steps", 0.0, 0.0);
+  record_dec_launch(true, 0, xp, x, -1);
+  // dec_persist_variant took the shape but no candidate is co-resident (more than two row tiles at one workgroup per
+  // CU): attn_sync_regions still names the headers to the caller's harvest, so they must not be stale memory
+  if (pvar) S2S_TRY(launch_sync_prep(st, k.fsync, 256, nullptr, k.fhdr));
   if (d.hf > 0) hipLaunchKernelGGL(dec_hyb_fold, dim3((d.Sc + 255) / 256), dim3(256), 0, st, k);
   if (d.lstm) hipLaunchKernelGGL(dec_lstm_pack, dim3(256), dim3(256), 0, st, k);
   const bool fold = dec_fold_f45(d);
@@ -1736,15 +1766,20 @@ int attn_fwd(hipStream_t st, const AttnDims& d, const float* h, const int* label
       k.UPS = dr.splits;
       k.UPMN = dr.mn;
     }
+    decide("dec.head_sums_slabs", dr.splits > 1);  // the head launch below really has slabs to sum
   }
+  decide("dec.merged_head", merge_head);
   if (merge_head) {
     const bool hb = attn_head_bwd_fused(d);
     k.dlogp = hb ? d.dlogp_early : nullptr;
+    decide("dec.head_bwd_fused", hb);
     hipLaunchKernelGGL(dec_xcd_alpha_vbar_head, dim3(T * B + ((d.Sc + 63) / 64) * B + (rows + 3) / 4), dim3(256),
                        4 * (d.M + (hb ? d.O : 0)) * sizeof(float), st, k, x, rows);
   }
-  else
+  else {
+    decide("dec.head_bwd_fused", 0);
     hipLaunchKernelGGL(dec_mlp_head, dim3((rows + 3) / 4), dim3(256), 4 * d.M * sizeof(float), st, k, rows);
+  }
   S2S_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -1854,6 +1889,7 @@ int attn_bwd_core(hipStream_t st, const AttnDims& d, const float* h, const int* 
     {
       ProfScope ps(st, xp.var == 3 ? "dec_bwd_xcd_lstm" : "dec_bwd_xcd", dec_flops(d, true),
                    8.0 * d.T * d.B * d.L * (double)(d.Sc + d.A));
+      record_dec_launch(false, xp.var == 3 ? 3 : 2, xp, x, -1);
       S2S_TRY(xp.var == 3 ? launch_xcd_lstm(false, st, k, x, y) : launch_xcd(xp, false, st, k, x));
     }
     // dVh / dwe (dec_xcd_dvh) beside the alpha^T dc GEMMs when split; both feed dh
@@ -1888,6 +1924,7 @@ int attn_bwd_core(hipStream_t st, const AttnDims& d, const float* h, const int* 
   } else if (pb.fn) {
     S2S_TRY(launch_sync_prep(st, k.bsync, k.bsync_bytes, nullptr, k.bhdr));
     ProfScope ps(st, "dec_bwd_persist", 0.0, 0.0);
+    record_dec_launch(false, 1, xp, x, pb.res);
     S2S_TRY(launch_persist(pb, pgrid, st, k));
     S2S_CHECK_HIP(hipGetLastError());
   } else {
@@ -1902,6 +1939,8 @@ int attn_bwd_core(hipStream_t st, const AttnDims& d, const float* h, const int* 
     S2S_TRY(zero_async(st, k.PDG, sizeof(float) * (size_t)B * k.NCH * d.hk * Sc));
   }
   ProfScope ps(st, "dec_bwd_steps", 0.0, 0.0);
+  record_dec_launch(false, 0, xp, x, -1);
+  if (pvar) S2S_TRY(launch_sync_prep(st, k.bsync, 256, nullptr, k.bhdr));  // (as in attn_fwd: a header the harvest reads)
   for (int t = T - 1; t >= 0; --t) {
     k.t = t;
     if (d.lstm) {
@@ -2505,6 +2544,7 @@ extern "C" void s2s_debug_dec_mode(int m) { s2s::g_dec_mode_force = m; }
 extern "C" void s2s_debug_dec_pf(int on) {  // 0: the XCD decoder's per-term attention form everywhere (A/B, tests)
   const int v = on ? 1 : 0;
   (void)hipMemcpyToSymbol(HIP_SYMBOL(s2s::g_dec_pf), &v, sizeof(int));
+  s2s::g_dec_pf_host = v;
 }
 extern "C" int s2s_debug_dec_stamps(void* fwd, void* bwd) {
   s2s::g_dec_stamps[0] = static_cast<unsigned long long*>(fwd);

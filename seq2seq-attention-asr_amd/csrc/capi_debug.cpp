@@ -1,9 +1,13 @@
 // The s2s_debug_* entry points of the C-ABI layer: diagnostics, test probes and A/B knobs exported by libs2s_hip.so
 // but not part of the C ABI header (include/s2s_hip.h).  (The kernels' own knobs sit beside their kernels.)
 #include <atomic>
+#include <map>
+#include <mutex>
 #include <string>
+#include <utility>
 
 #include "ctx.h"
+#include "decisions.h"
 #include "gru_persist.h"
 #include "step_knobs.h"
 
@@ -150,6 +154,30 @@ int s2s::inject_abort_take() {
   while (v > 0 && !g_inject_abort.compare_exchange_weak(v, v - 1)) {
   }
   return v > 0 ? 1 : 0;
+}
+// the record of dispatch decisions (decisions.h): name -> (last value, count), filled by the code that decides
+static std::mutex g_decisions_mu;
+static std::map<std::string, std::pair<long, long>> g_decisions;
+std::atomic<int> s2s::g_decisions_on{0};
+void s2s::decision_store(const char* name, long value) {
+  std::lock_guard<std::mutex> lock(g_decisions_mu);
+  std::pair<long, long>& e = g_decisions[name];
+  e.first = value;
+  e.second += 1;
+}
+extern "C" void s2s_debug_decisions(int on) { s2s::g_decisions_on.store(on ? 1 : 0, std::memory_order_relaxed); }
+extern "C" void s2s_debug_decisions_clear() {
+  std::lock_guard<std::mutex> lock(g_decisions_mu);
+  g_decisions.clear();
+}
+// 1 and *value / *count when `name` was recorded since the last clear, else 0 (and both 0)
+extern "C" int s2s_debug_decision(const char* name, long* value, long* count) {
+  std::lock_guard<std::mutex> lock(g_decisions_mu);
+  const auto it = name ? g_decisions.find(name) : g_decisions.end();
+  const bool have = it != g_decisions.end();
+  if (value) *value = have ? it->second.first : 0;
+  if (count) *count = have ? it->second.second : 0;
+  return have ? 1 : 0;
 }
 // the model step's knobs (step_knobs.h)
 extern "C" void s2s_debug_fuse_dh(int on) { g_fuse_dh = on; }

@@ -21,6 +21,7 @@
 #include <cstring>
 #include <vector>
 
+#include "decisions.h"
 #include "gru_persist.h"
 #include "skinny.h"
 
@@ -407,8 +408,12 @@ int gru_layer_fwd(hipStream_t st, const GruLayerIO& io, void* scratch, size_t sc
     f.pack = io.pack_jobs;
     f.excl = io.excl;
     f.status = io.status;
+    decide("gru.fwd.path", 1);
+    decide("gru.fused_xproj", fuse);
     return gru_persist_fwd(st, f, sync);
   }
+  decide("gru.fwd.path", 0);
+  decide("gru.fused_xproj", 0);
   const dim3 g1(2 * H / 16, (B + 15) / 16, nd), g2(H / 16, (B + 15) / 16, nd);
   ProfScope ps(st, "gru_fwd_steps", 2.0 * nd * B * L * 3.0 * H * H, 0.0);
   for (int s = 0; s < L; ++s) {
@@ -503,8 +508,12 @@ int gru_layer_bwd_core(hipStream_t st, const GruLayerIO& io, const GruLayerGrad&
       f.wx = io.x; f.wldx = io.ldx; f.wD = D;
       f.wpart = gr.wpart;
     }
+    decide("gru.bwd.path", 1);
+    decide("gru.fused_dy", yfuse);
     S2S_TRY(gru_persist_bwd(st, f, sync));
   } else {
+    decide("gru.bwd.path", 0);
+    decide("gru.fused_dy", 0);
     ProfScope ps(st, "gru_bwd_steps", 2.0 * nd * B * L * 3.0 * H * H, 0.0);
     hipLaunchKernelGGL(gru_bwd_init, dim3((B * H + 255) / 256, nd), dim3(256), 0, st, a);
     const dim3 g1(H / 16, (B + 15) / 16, nd);

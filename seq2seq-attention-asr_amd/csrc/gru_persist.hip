@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "decisions.h"
 #include "gru.h"
 #include "gru_persist.h"
 #include "handoff.h"
@@ -1645,6 +1646,8 @@ int gru_persist_fwd(hipStream_t st, const GruPersistFwd& f, void* sync) {
   const double xflops = f.x ? 2.0 * f.B * f.L * 3.0 * f.ndir * f.H * f.Kx : 0.0;
   const double xbytes = f.x ? 4.0 * ((double)f.B * f.L * f.Kx + 3.0 * f.ndir * f.H * f.Kx + 3.0 * f.ndir * f.B * f.L * f.H)
                             : 0.0;
+  decide("gru.local", a.allow_local);
+  decide("gru.ring", a.ring);
   ProfScope ps(st, "gru_fwd_persist", 2.0 * f.ndir * f.B * f.L * 3.0 * f.H * f.H + xflops,
                4.0 * f.ndir * (3.0 * f.H * f.H + (double)f.B * f.L * (3 * f.H + 5 * f.H + f.H)) + xbytes);
   S2S_TRY(launch(st, a, f.excl != 0, true));
@@ -1730,6 +1733,12 @@ int gru_persist_bwd(hipStream_t st, const GruPersistBwd& b, void* sync) {
   const double wbytes = b.wgrad ? 4.0 * ((double)b.B * b.L * (b.ndir * 3.0 * b.H + b.ndir * 2.0 * b.H + b.wD) +
                                          2.0 * b.ndir * 3.0 * b.H * (b.H + b.wD))
                                 : 0.0;
+  decide("gru.local", a.allow_local);
+  decide("gru.ring", a.ring);
+  if (a.fused) {  // how the fused dy's units are cut and dealt (xproj_split, xproj_group)
+    decide("gru.xp_split", a.xq.sB > 0 ? a.xq.sA * 1000L + a.xq.sB : 0);
+    decide("gru.xp_group", a.xq.G);
+  }
   ProfScope ps(st, "gru_bwd_persist", 2.0 * b.ndir * b.B * b.L * 3.0 * b.H * b.H + yflops + wflops,
                4.0 * b.ndir * (3.0 * b.H * b.H + (double)b.B * b.L * (5 * b.H + b.H + 3 * b.H)) + ybytes + wbytes);
   S2S_TRY(launch(st, a, b.excl != 0, false));

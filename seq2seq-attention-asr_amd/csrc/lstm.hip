@@ -16,6 +16,7 @@
 // Saved per direction: sv (B, L, 8H) = i | f | g | o | c | c_{t-1} | h_{t-1} | tanh(c).
 #include "lstm.h"
 
+#include "decisions.h"
 #include "skinny.h"
 
 namespace s2s {
@@ -416,6 +417,7 @@ int lstm_layer_fwd(hipStream_t st, const LstmLayerIO& io, void* scratch, size_t 
   }
   a.B = B; a.L = L; a.H = H; a.peep = io.peep; a.len = io.len;
   const dim3 gg(4 * H / 16, (B + 15) / 16, nd), gc((B * H + 255) / 256, nd), go(H / 16, (B + 15) / 16, nd);
+  decide("lstm.fwd.path", 0);
   ProfScope ps(st, "lstm_fwd_steps", 2.0 * nd * B * L * 4.0 * H * H * (io.peep ? 1.75 : 1.0), 0.0);
   const dim3 gs(H / 16, (B + 15) / 16, nd);
   for (int s = 0; s < L; ++s) {
@@ -465,6 +467,7 @@ int lstm_layer_bwd(hipStream_t st, const LstmLayerIO& io, const LstmLayerGrad& g
     }
     S2S_TRY(lstm_persist_bwd(st, b, c.sync, io.status));
   } else {
+    decide("lstm.bwd.path", 0);
     ProfScope ps(st, "lstm_bwd_steps", 2.0 * nd * B * L * 4.0 * H * H * (io.peep ? 1.75 : 1.0), 0.0);
     const dim3 gs(H / 16, (B + 15) / 16, nd);
     for (int s = L - 1; s >= 0; --s) {

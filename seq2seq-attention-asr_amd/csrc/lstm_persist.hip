@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "decisions.h"
 #include "handoff.h"
 #include "lstm.h"
 #include "skinny.h"
@@ -375,6 +376,7 @@ int lstm_persist_fwd(hipStream_t st, const LstmPersistArgs& f, void* sync, unsig
   }
   S2S_TRY(launch_sync_prep(st, sync, prep_bytes_l(f.B, f.H, a.nchains, a.nmem)));
   {
+    decide("lstm.fwd.path", 1);
     ProfScope ps(st, "lstm_fwd_persist", 2.0 * f.ndir * f.B * f.L * 4.0 * f.H * f.H,
                  4.0 * f.ndir * (4.0 * f.H * f.H + (double)f.B * f.L * (4 * f.H + 8 * f.H + f.H)));
     switch (f.H / 64) {
@@ -402,6 +404,7 @@ int lstm_persist_bwd(hipStream_t st, const LstmPersistArgs& b, void* sync, unsig
   }
   S2S_TRY(launch_sync_prep(st, sync, prep_bytes_l(b.B, b.H, a.nchains, a.nmem)));
   {
+    decide("lstm.bwd.path", 1);
     ProfScope ps(st, "lstm_bwd_persist", 2.0 * b.ndir * b.B * b.L * 4.0 * b.H * b.H,
                  4.0 * b.ndir * (4.0 * b.H * b.H + (double)b.B * b.L * (6 * b.H + b.H + 4 * b.H)));
     switch (4 * b.H / 128) {

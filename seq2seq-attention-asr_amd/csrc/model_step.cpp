@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "decisions.h"
 #include "gru.h"
 #include "gru_persist.h"
 #include "handoff.h"
@@ -251,6 +252,7 @@ int model_step_impl(hipStream_t st, hipStream_t side, hipEvent_t* ev, hipEvent_t
   // two sync regions; a launch with spare slots prepares the next launch's region itself, so only the
   // first launch has a sync_prep in front of it
   int glaunch = 0;
+  decide("step.sync_handover", g_sync_handover);
   bool gprepared = head_fused;  // the step head prepared the first launch's region
   bool gused[2] = {false, false};  // a persistent launch of this step used the region (harvested at the end)
   auto hand_over = [&](GruLayerIO& io, bool fwd, const GruLayerIO* next) {
@@ -363,6 +365,8 @@ int model_step_impl(hipStream_t st, hipStream_t side, hipEvent_t* ev, hipEvent_t
       gr.wgrad = 1;
       gr.wpart = w.wpart;
     }
+    if (l == 0) decide("step.bptt_wgrad_in", wg_in);
+    if (l == nl - 1) decide("step.fuse_dh", gr.yalpha != nullptr);  // the decoder's dh inside the top BPTT launch
     if (defer && pending >= 0) gr.prep_event = ev[1 + pending];
     S2S_TRY(gru_layer_bwd_core(st, io, gr, w.dA[l], w.scratch, w.scratch_bytes));
     if (defer) {

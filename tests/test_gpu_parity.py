@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import paths
 from oracle import s2s_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -61,11 +62,15 @@ def test_gru_layer_matches_oracle(s2s, B, L, D, H, bidir):
         mod = s2s.RNN(cells[0], reverse=(L % 2 == 1))
     mod.cuda()
     xs = cu(x)
-    y = mod.forward(xs).cpu().numpy()
-    dy = rng.standard_normal(y.shape)
-    mod.zeroGradParameters()
-    dx = mod.backward(xs, cu(dy), 0.5).cpu().numpy()
-    torch.cuda.synchronize()
+    with paths.decisions() as dec:
+        y = mod.forward(xs).cpu().numpy()
+        dy = rng.standard_normal(y.shape)
+        mod.zeroGradParameters()
+        dx = mod.backward(xs, cu(dy), 0.5).cpu().numpy()
+        torch.cuda.synchronize()
+    # the persistent layer kernels are instantiated for H in {64, 128, 256, 512}; H = 16 and 32 run the per-step launches
+    paths.took(dec, "gru.fwd.path", 1 if H == 64 else 0)
+    paths.took(dec, "gru.bwd.path", 1 if H == 64 else 0)
     revs = [False, True] if bidir else [mod.reverse]
     dx_ref = np.zeros_like(x)
     for i, (W, rev) in enumerate(zip(Ws, revs)):
@@ -192,22 +197,28 @@ def test_persistent_lstm_matches_oracle_and_per_step(s2s, monkeypatch, local, B,
 
 ATT_CASES = [
     # B, L, T, A, Sc, S, O, M, K, penalty
+    # widths without a persistent or XCD-local instantiation: the per-step launches
     (3, 20, 5, 32, 48, 32, 7, 4, 3, 0.0),
     (4, 33, 6, 64, 64, 48, 29, 8, 7, 0.0),
     (2, 16, 4, 32, 32, 16, 5, 3, 2, 0.25),
     (19, 8, 3, 16, 16, 16, 62, 5, 7, 0.0),
-    # shapes served by the persistent decoder kernels (S=64, A=128, Sc=128), ragged B and L
+    # the small instantiated widths (S=64, A=128, Sc=128), ragged B and L: dec_xcd_plan takes them first, so they run
+    # the XCD-local decoder (the persistent decoder kernels serve these widths only where the plan declines:
+    # test_forced_decoder_paths_match_oracle, test_decoder_auto_mode_fallbacks_match_oracle)
     (5, 37, 6, 128, 128, 64, 29, 4, 7, 0.3),
     (18, 16, 4, 128, 128, 64, 62, 8, 7, 0.0),
-    # vocabularies wider than one wave: the MLP head's and the LogSoftMax's stride over outputDepth
+    # vocabularies wider than one wave: the MLP head's and the LogSoftMax's stride over outputDepth (per-step)
     (3, 20, 5, 32, 48, 32, 100, 4, 3, 0.0),
     (5, 9, 4, 32, 48, 32, 65, 4, 3, 0.0),
 ]
+# the path that serves each row, in ATT_CASES' order: the first four and the last two per-step, the two between XCD-local
+ATT_PATHS = [paths.STEPS] * 4 + [paths.XCD] * 2 + [paths.STEPS] * 2
 
 
 @pytest.mark.parametrize("B,L,T,A,Sc,S,O,M,K,pen", ATT_CASES)
 def test_attention_decoder_matches_oracle(s2s, B, L, T, A, Sc, S, O, M, K, pen):
-    _check_attention(s2s, B, L, T, A, Sc, S, O, M, K, pen)
+    path = ATT_PATHS[ATT_CASES.index((B, L, T, A, Sc, S, O, M, K, pen))]
+    _check_attention(s2s, B, L, T, A, Sc, S, O, M, K, pen, expect_path=path)
 
 
 # shapes served by the XCD-local decoder kernels (dec_xcd.inc): chains of U utterances on one XCD;
@@ -237,9 +248,10 @@ def test_xcd_decoder_matches_oracle(s2s, B, L, T, A, Sc, S, O, M, K, pen, local)
     fn.argtypes = [ctypes.c_int]
     fn(local)
     try:
-        _check_attention(s2s, B, L, T, A, Sc, S, O, M, K, pen)
+        dec = _check_attention(s2s, B, L, T, A, Sc, S, O, M, K, pen, expect_path=paths.XCD)
     finally:
         fn(1)
+    paths.took(dec, "dec.allow_local", local)
 
 
 # chunks too long for LDS residency (> 32 frames): h / Vh rows streamed from global memory each step
@@ -252,7 +264,8 @@ XCD_STREAM_CASES = [
 @pytest.mark.parametrize("B,L,T,A,Sc,S,O,M,K,pen", XCD_STREAM_CASES)
 def test_xcd_decoder_streamed_chunks_match_oracle(s2s, B, L, T, A, Sc, S, O, M, K, pen):
     """LibriSpeech-length utterances (config 4: L = 400) on the XCD-local decoder with streamed chunks."""
-    _check_attention(s2s, B, L, T, A, Sc, S, O, M, K, pen)
+    dec = _check_attention(s2s, B, L, T, A, Sc, S, O, M, K, pen, expect_path=paths.XCD)
+    paths.took(dec, "dec.res", 1)
 
 
 @pytest.mark.parametrize("B,L,T,A,Sc,S,O", [(32, 128, 12, 512, 512, 256, 62), (21, 50, 9, 128, 128, 64, 29)])
@@ -263,20 +276,32 @@ def test_xcd_decoder_streamed_bitwise_equals_resident(s2s, monkeypatch, B, L, T,
     h = cu(rng.standard_normal((B, L, A)) * 0.5)
     labels = cu(rng.integers(0, O, (B, T)), torch.int32)
     dlogp = cu(rng.standard_normal((B, T, O)))
-    outs = {}
+    outs, decs = {}, {}
     for stream in ("2", "0", "1"):  # resident (default at these shapes), no residency, Vh-only
         monkeypatch.setenv("S2S_DEC_STREAM", stream)
-        logp = att.forward([h, labels]).clone()
-        att.zeroGradParameters()
-        dh = att.backward([h, None], dlogp)[0].clone()
+        with paths.decisions() as dec:
+            logp = att.forward([h, labels]).clone()
+            att.zeroGradParameters()
+            dh = att.backward([h, None], dlogp)[0].clone()
         outs[stream] = [logp, dh] + [g.clone() for g in att.parameters()[1]]
+        decs[stream] = dec
     torch.cuda.synchronize()
+    for stream in ("2", "0", "1"):
+        paths.took(decs[stream], "dec.fwd.path", paths.XCD)
+        paths.took(decs[stream], "dec.bwd.path", paths.XCD)
+        paths.took(decs[stream], "dec.res", int(stream))
+        assert decs[stream].count("dec.res") == 2  # the forward's launch and the backward's
+    paths.differ(decs["2"], decs["0"], "dec.res")
+    paths.differ(decs["2"], decs["1"], "dec.res")
     for mode in ("0", "1"):
         for i, (a, b) in enumerate(zip(outs["2"], outs[mode])):
             assert torch.equal(a, b), f"mode {mode} tensor {i} differs: max |d| = {(a - b).abs().max().item():.3e}"
 
 
-def _check_attention(s2s, B, L, T, A, Sc, S, O, M, K, pen, kW=10, nF=0):
+def _check_attention(s2s, B, L, T, A, Sc, S, O, M, K, pen, kW=10, nF=0, expect_path=None):
+    """One forward + backward of nn.Attention against the float64 oracle.  expect_path: the decoder path (paths.STEPS /
+    PERSIST / XCD / XCD_LSTM, or a tuple of accepted ones) that both the forward's and the backward's launch code
+    must have recorded.  Returns the decision reader of the two calls."""
     rng = np.random.default_rng(L * 7 + T)
     torch.manual_seed(L * 7 + T)  # module init draws from torch's generator
     cfg = orc.ModelConfig(inputFrameSize=8, hiddenFrameSize=16, outputFrameSize=A // 2, scoreDepth=Sc, stateDepth=S,
@@ -291,20 +316,30 @@ def _check_attention(s2s, B, L, T, A, Sc, S, O, M, K, pen, kW=10, nF=0):
     h = rng.standard_normal((B, L, A)) * 0.5
     labels = rng.integers(0, O, (B, T)).astype(np.int32)
     hs = cu(h)
-    logp = att.forward([hs, cu(labels, torch.int32)]).cpu().numpy()
+    dlogp = rng.standard_normal((B, T, O))
+    with paths.decisions() as dec:
+        logp = att.forward([hs, cu(labels, torch.int32)]).cpu().numpy()
+        alpha = att.alpha().cpu().numpy()
+        ind = att.mono_ind().cpu().numpy() if pen > 0 else None
+        att.zeroGradParameters()
+        dh = att.backward([hs, None], cu(dlogp), 0.5)[0].cpu().numpy()
+    if expect_path is not None:
+        want = expect_path if isinstance(expect_path, tuple) else (expect_path,)
+        for name in ("dec.fwd.path", "dec.bwd.path"):
+            assert dec.count(name) == 1, f"{name} recorded {dec.count(name)} times"
+            assert dec[name] in want, f"{name} = {dec[name]}, expected {want} (0 steps, 1 persist, 2 xcd, 3 xcd_lstm)"
+        assert dec["dec.fwd.path"] == dec["dec.bwd.path"]
     lref, cache = orc.attention_fwd(h, labels, P, cfg)
     assert_rel(logp, lref, "logp")
-    assert_rel(att.alpha().cpu().numpy(), cache["alpha"], "alpha")
+    assert_rel(alpha, cache["alpha"], "alpha")
     if pen > 0:
-        _adopt_mono_decisions(att, cache, L)
-    dlogp = rng.standard_normal(logp.shape)
-    att.zeroGradParameters()
-    dh = att.backward([hs, None], cu(dlogp), 0.5)[0].cpu().numpy()
+        _adopt_mono_decisions(ind, cache, L)
     G = orc.zeros_like_params(P)
     dhr = orc.attention_bwd(P, cfg, cache, dlogp, G, 0.5)
     assert_rel(dh, dhr, "dh")
     for name, g in zip(P.keys(), att.parameters()[1]):
         assert_rel(g.cpu().numpy(), G[name], "d" + name)
+    return dec
 
 
 @pytest.mark.parametrize("B,L,T,A,Sc,S,O,M,K,pen,kW,nF", [
@@ -320,14 +355,14 @@ def test_hybrid_attention_matches_oracle(s2s, B, L, T, A, Sc, S, O, M, K, pen, k
     _check_attention(s2s, B, L, T, A, Sc, S, O, M, K, pen, kW, nF)
 
 
-def _adopt_mono_decisions(att, cache, L, margin=1e-4):
+def _adopt_mono_decisions(ind, cache, L, margin=1e-4):
     """MonotonicAlignment's gradient depends on the discrete decisions 1[penalty_t > 0]
     (MonotonicAlignment.lua:27-39, 44-77).  Their statistic sum_l (L-l)(alpha_t - alpha_{t-1}) sits
     within fp32 noise of 0 whenever attention barely moves between steps (typical of random weights),
     where any fp32 implementation -- the reference's CudaTensor path too -- may decide differently from
     the float64 oracle.  Require the GPU's decisions to agree wherever the statistic is clear of 0,
     then run the oracle's backward under the GPU's decisions."""
-    gi = att.mono_ind().cpu().numpy().astype(np.float64)
+    gi = np.asarray(ind).astype(np.float64)
     a = cache["alpha"]
     prev = np.concatenate([np.zeros_like(a[:, :1]), a[:, :-1]], 1)
     stat = ((L - np.arange(L))[None, None, :] * (a - prev)).sum(-1)
@@ -490,7 +525,17 @@ def test_model_step_degenerate_shapes(s2s, B, L, T):
 def test_model_step_chorowski_config2(s2s):
     """BASELINE config 2 at full size: B=32, L=128, T=40, F=123, 3x BiGRU(256), Sc=512, O=62."""
     cfg_o, model, P, x, labels = _model_case(s2s, {}, 32, 128, 40)
-    _check_step(model, cfg_o, P, x, labels)
+    with paths.decisions() as dec:
+        _check_step(model, cfg_o, P, x, labels)
+    # run eagerly, the step takes the benched kernels: the persistent BiGRU launches with the x-projection and the dy
+    # of the layer above computed inside them, and the XCD-local decoder
+    for name in ("gru.fwd.path", "gru.bwd.path"):
+        paths.took(dec, name, 1)
+        assert dec.count(name) == cfg_o.numLayers
+    paths.took(dec, "dec.fwd.path", paths.XCD)
+    paths.took(dec, "dec.bwd.path", paths.XCD)
+    paths.took(dec, "gru.fused_xproj", 1)
+    paths.took(dec, "gru.fused_dy", 1)
 
 
 def test_model_step_config2_dims_b45_graph(s2s):
@@ -605,17 +650,29 @@ def test_fused_dy_dealing_does_not_change_the_step(s2s, B):
     g = torch.Generator().manual_seed(B)
     x = torch.randn(B, 96, cfg.inputFrameSize, generator=g).cuda()
     lab = torch.randint(0, cfg.outputDepth, (B, 20), generator=g).to(torch.int32).cuda()
-    outs = {}
+    outs, decs = {}, {}
     try:
         for arm, (grp, fused) in {"grouped": (1, 1), "round-robin": (0, 1), "gemm": (0, 0)}.items():
             fg(grp)
             fd(fused)
-            nll, logp = model.step(x, lab)
-            torch.cuda.synchronize()
+            with paths.decisions() as dec:
+                nll, logp = model.step(x, lab)
+                torch.cuda.synchronize()
             outs[arm] = (logp.clone(), model.grads.clone())
+            decs[arm] = dec
     finally:
         fg(1)
         fd(1)
+    # each arm ran what it names: the dy units dealt in per-XCD groups (gru.xp_group = the number of groups) or
+    # round-robin (0) inside the BPTT launches, or the dX GEMM in front of them (the record keeps the step's last BPTT
+    # launch, the first layer's, whose dy is the second layer's dX)
+    assert decs["grouped"].count("gru.xp_group") > 0 and decs["grouped"]["gru.xp_group"] > 0
+    paths.took(decs["round-robin"], "gru.xp_group", 0)
+    paths.differ(decs["grouped"], decs["round-robin"], "gru.xp_group")
+    paths.took(decs["grouped"], "gru.fused_dy", 1)
+    paths.took(decs["round-robin"], "gru.fused_dy", 1)
+    paths.took(decs["gemm"], "gru.fused_dy", 0)
+    paths.differ(decs["round-robin"], decs["gemm"], "gru.fused_dy")
     assert torch.equal(outs["grouped"][0], outs["round-robin"][0])
     assert torch.equal(outs["grouped"][1], outs["round-robin"][1])
     ga, gb = outs["grouped"][1], outs["gemm"][1]
@@ -636,15 +693,22 @@ def test_mlp_head_summing_slabs_is_bitwise_the_reduce(s2s, B):
     g = torch.Generator().manual_seed(7 + B)
     x = torch.randn(B, 96, cfg.inputFrameSize, generator=g).cuda()
     lab = torch.randint(0, cfg.outputDepth, (B, 40), generator=g).to(torch.int32).cuda()
-    outs = {}
+    outs, decs = {}, {}
     try:
         for arm, on in (("reduce", 0), ("head", 1)):
             fn(on)
-            nll, logp = model.step(x, lab)
-            torch.cuda.synchronize()
+            with paths.decisions() as dec:
+                nll, logp = model.step(x, lab)
+                torch.cuda.synchronize()
             outs[arm] = (nll.clone(), logp.clone(), model.grads.clone())
+            decs[arm] = dec
     finally:
         fn(1)
+    # (dec.head_sums_slabs: the MLP GEMM really left split-K slabs for the merged head launch to sum)
+    paths.differ(decs["reduce"], decs["head"], "dec.head_sums_slabs")
+    for arm, on in (("reduce", 0), ("head", 1)):
+        paths.took(decs[arm], "dec.merged_head", 1)
+        paths.took(decs[arm], "dec.head_sums_slabs", on)
     for a, b in zip(outs["reduce"], outs["head"]):
         assert torch.equal(a, b)
 
@@ -660,19 +724,31 @@ def test_mlp_head_backward_in_the_forward_head_launch_is_bitwise_separate(s2s, B
     fn = _lib.lib.s2s_debug_merge_alpha_head
     fn.argtypes = [ctypes.c_int]
     cfg = s2s.ModelConfig()
-    model = s2s.ChorowskiBaseline(cfg, graph=False)
+    # (the step head writes the loss seed only in the side-stream layout, the bench's -- the overlap context on a
+    # stream of its own: on the default stream no arm runs the head's backward in the forward's launch)
+    model = s2s.ChorowskiBaseline(cfg, graph=False, overlap=True)
     g = torch.Generator().manual_seed(17 + B)
     x = torch.randn(B, 96, cfg.inputFrameSize, generator=g).cuda()
     lab = torch.randint(0, cfg.outputDepth, (B, 40), generator=g).to(torch.int32).cuda()
-    outs = {}
+    st = torch.cuda.Stream()
+    st.wait_stream(torch.cuda.current_stream())
+    outs, decs = {}, {}
     try:
         for arm, on in (("separate", 0), ("fused", 1)):
             fn(on)
-            nll, logp = model.step(x, lab)
-            torch.cuda.synchronize()
+            with paths.decisions() as dec, torch.cuda.stream(st):
+                nll, logp = model.step(x, lab, stream=st)
+                torch.cuda.synchronize()
             outs[arm] = (nll.clone(), logp.clone(), model.grads.clone())
+            decs[arm] = dec
     finally:
         fn(1)
+    paths.differ(decs["separate"], decs["fused"], "dec.merged_head")
+    paths.differ(decs["separate"], decs["fused"], "dec.head_bwd_fused")
+    for arm, on in (("separate", 0), ("fused", 1)):
+        paths.took(decs[arm], "dec.fwd.path", paths.XCD)
+        paths.took(decs[arm], "dec.merged_head", on)
+        paths.took(decs[arm], "dec.head_bwd_fused", on)
     for a, b in zip(outs["separate"], outs["fused"]):
         assert torch.equal(a, b)
 
@@ -692,15 +768,23 @@ def test_decoder_four_row_products_match_the_sixteen_row_form(s2s, B):
     g = torch.Generator().manual_seed(11 + B)
     x = torch.randn(B, 96, cfg.inputFrameSize, generator=g).cuda()
     lab = torch.randint(0, cfg.outputDepth, (B, 40), generator=g).to(torch.int32).cuda()
-    outs = {}
+    outs, decs = {}, {}
     try:
         for arm, on in (("r16", 0), ("r4", 1), ("r4b", 1)):
             fn(on)
-            nll, logp = model.step(x, lab)
-            torch.cuda.synchronize()
+            with paths.decisions() as dec:
+                nll, logp = model.step(x, lab)
+                torch.cuda.synchronize()
             outs[arm] = (nll.clone(), logp.clone(), model.grads.clone())
+            decs[arm] = dec
     finally:
         fn(1)
+    paths.differ(decs["r16"], decs["r4"], "dec.r4")
+    for arm, on in (("r16", 0), ("r4", 1), ("r4b", 1)):
+        paths.took(decs[arm], "dec.fwd.path", paths.XCD)
+        paths.took(decs[arm], "dec.r4", on)
+        assert decs[arm].count("dec.r4") == 2  # the forward's launch and the backward's
+        assert decs[arm]["dec.U"] <= 4
     for a, b in zip(outs["r4"], outs["r4b"]):
         assert torch.equal(a, b)
     for a, b in zip(outs["r4"], outs["r16"]):
@@ -760,16 +844,25 @@ def test_decoder_attention_product_form_matches_the_per_term_form(s2s, B, L, T, 
     g = torch.Generator().manual_seed(7 + B + L)
     x = torch.randn(B, L, cfg.inputFrameSize, generator=g).cuda()
     lab = torch.randint(0, cfg.outputDepth, (B, T), generator=g).to(torch.int32).cuda()
-    outs = {}
+    outs, decs = {}, {}
     try:
         for arm, on in (("product", 1), ("per_term", 0)):
             fn(on)
-            model.step(x, lab)
-            _, logp = model.step(x, lab)
-            torch.cuda.synchronize()
+            with paths.decisions() as dec:
+                model.step(x, lab)
+                _, logp = model.step(x, lab)
+                torch.cuda.synchronize()
             outs[arm] = (logp.clone(), model.grads.clone())
+            decs[arm] = dec
     finally:
         fn(1)
+    # (dec.pf: the form the launches were told to take; which form a workgroup then takes is decided on the device)
+    paths.differ(decs["product"], decs["per_term"], "dec.pf")
+    for arm, on in (("product", 1), ("per_term", 0)):
+        paths.took(decs[arm], "dec.fwd.path", paths.XCD)
+        paths.took(decs[arm], "dec.bwd.path", paths.XCD)
+        paths.took(decs[arm], "dec.pf", on)
+        paths.took(decs[arm], "dec.res", 1 if L == 400 else 2)
     (la, ga), (lb, gb) = outs["product"], outs["per_term"]
     assert torch.isfinite(ga).all() and torch.isfinite(la).all()
     if vscale != 1.0:
@@ -801,15 +894,21 @@ def test_bptt_inlaunch_wgrad_matches_the_gemm(s2s, B, ragged):
         fl = torch.randint(L // 3, L + 1, (B,), generator=g).tolist()
         fl[0] = L
         kw = dict(frame_lengths=fl, label_lengths=[T] * B)
-    outs = {}
+    outs, decs = {}, {}
     try:
         for arm, on in (("gemm", 0), ("inlaunch", 1), ("again", 1)):
             fn(on)
-            model.step(x, lab, **kw)
-            torch.cuda.synchronize()
+            with paths.decisions() as dec:
+                model.step(x, lab, **kw)
+                torch.cuda.synchronize()
             outs[arm] = model.grads.clone()
+            decs[arm] = dec
     finally:
         fn(0)
+    paths.differ(decs["gemm"], decs["inlaunch"], "step.bptt_wgrad_in")
+    for arm, on in (("gemm", 0), ("inlaunch", 1), ("again", 1)):
+        paths.took(decs[arm], "step.bptt_wgrad_in", on)
+        paths.took(decs[arm], "gru.bwd.path", 1)
     H, D = cfg.hiddenFrameSize, cfg.inputFrameSize
     n0 = 6 * H * (H + D)  # layer 1's six (H, H + D) gate weights lead the flat gradient vector
     assert torch.equal(outs["inlaunch"], outs["again"])
@@ -839,23 +938,36 @@ def test_persistent_gru_bitwise_equals_per_step_launches(s2s, monkeypatch, local
     L, D = 40, 48
     x = cu(rng.standard_normal((B, L, D)))
     f, b = s2s.GRU(D, H), s2s.GRU(D, H)
-    outs = {}
+    outs, decs = {}, {}
     fn(local)
     fr(ring)
-    for mode in ("step", "persistent"):
-        monkeypatch.setenv("S2S_GRU_MODE", mode)
-        mod = s2s.BiRNN(f, b).cuda()
-        res = []
-        for rep in range(3):
-            y = mod.forward(x).clone()
-            mod.zeroGradParameters()
-            dy = torch.ones_like(y) * 0.01 + y * 0.5
-            dx = mod.backward(x, dy).clone()
-            res.append((y, dx, [g.clone() for g in f.gradWeight + b.gradWeight]))
-        torch.cuda.synchronize()
-        outs[mode] = res
-    fn(1)
-    fr(1)
+    try:
+        for mode in ("step", "persistent"):
+            monkeypatch.setenv("S2S_GRU_MODE", mode)
+            mod = s2s.BiRNN(f, b).cuda()
+            res = []
+            with paths.decisions() as dec:
+                for rep in range(3):
+                    y = mod.forward(x).clone()
+                    mod.zeroGradParameters()
+                    dy = torch.ones_like(y) * 0.01 + y * 0.5
+                    dx = mod.backward(x, dy).clone()
+                    res.append((y, dx, [g.clone() for g in f.gradWeight + b.gradWeight]))
+                torch.cuda.synchronize()
+            outs[mode] = res
+            decs[mode] = dec
+    finally:
+        fn(1)
+        fr(1)
+    for mode, path in (("step", 0), ("persistent", 1)):
+        for name in ("gru.fwd.path", "gru.bwd.path"):
+            paths.took(decs[mode], name, path)
+            assert decs[mode].count(name) == 3
+    paths.differ(decs["step"], decs["persistent"], "gru.fwd.path")
+    paths.differ(decs["step"], decs["persistent"], "gru.bwd.path")
+    # the persistent arm's hand-off form is the one the parameters name (L = 40 > the ring's 4 slots)
+    paths.took(decs["persistent"], "gru.local", local)
+    assert (decs["persistent"]["gru.ring"] > 0) == bool(ring), decs["persistent"]["gru.ring"]
     for rep in range(3):
         ys, dxs, gs = outs["step"][rep]
         yp, dxp, gp = outs["persistent"][rep]
@@ -877,18 +989,26 @@ def test_persistent_decoder_bitwise_equals_per_step_launches(s2s, monkeypatch, B
     h = cu(rng.standard_normal((B, L, A)) * 0.5)
     labels = cu(rng.integers(0, O, (B, T)), torch.int32)
     dlogp = cu(rng.standard_normal((B, T, O)))
-    outs = {}
-    for mode in ("step", "persist"):
-        monkeypatch.setenv("S2S_DEC_MODE", mode)
+    outs, decs = {}, {}
+    # (the arms are selected in-process: S2S_DEC_MODE is read once, by the first attention call of the process)
+    for mode, force in (("step", paths.MODE_STEP), ("persist", paths.MODE_PERSIST)):
         res = []
-        for _ in range(2):
-            logp = att.forward([h, labels]).clone()
-            alpha = att.alpha().clone()
-            att.zeroGradParameters()
-            dh = att.backward([h, None], dlogp)[0].clone()
-            res.append([logp, alpha, dh] + [g.clone() for g in att.parameters()[1]])
-        torch.cuda.synchronize()
+        with paths.dec_mode(force), paths.decisions() as dec:
+            for _ in range(2):
+                logp = att.forward([h, labels]).clone()
+                alpha = att.alpha().clone()
+                att.zeroGradParameters()
+                dh = att.backward([h, None], dlogp)[0].clone()
+                res.append([logp, alpha, dh] + [g.clone() for g in att.parameters()[1]])
+            torch.cuda.synchronize()
         outs[mode] = res
+        decs[mode] = dec
+    for mode, path in (("step", paths.STEPS), ("persist", paths.PERSIST)):
+        for name in ("dec.fwd.path", "dec.bwd.path"):
+            paths.took(decs[mode], name, path)
+            assert decs[mode].count(name) == 2
+    paths.differ(decs["step"], decs["persist"], "dec.fwd.path")
+    paths.differ(decs["step"], decs["persist"], "dec.bwd.path")
     names = ["logp", "alpha", "dh"] + ["d" + n for n in s2s.Attention.PARAM_NAMES]
     for rep in range(2):
         for name, a, b in zip(names, outs["step"][rep], outs["persist"][rep]):
@@ -896,6 +1016,136 @@ def test_persistent_decoder_bitwise_equals_per_step_launches(s2s, monkeypatch, B
                 assert (a - b).abs().max().item() <= 1e-6 * a.abs().max().item(), f"dh (rep {rep})"
                 continue
             assert torch.equal(a, b), f"{name} differs (rep {rep}): max |d| = {(a - b).abs().max().item():.3e}"
+
+
+# (B, L, T, A, Sc, S, O, M, K, pen) for the forced per-step and persistent decoder paths
+FORCED_CASES = [
+    # the small instantiated widths
+    (21, 50, 9, 128, 128, 64, 29, 4, 7, 0.2),
+    (1, 1, 1, 128, 128, 64, 11, 4, 3, 0.0),
+    (17, 16, 1, 128, 128, 64, 62, 8, 7, 0.0),   # two row tiles, the second with one row
+    (33, 17, 3, 128, 128, 64, 65, 4, 3, 0.0),   # ragged tile, ragged 16-frame chunk, vocabulary wider than a wave
+    (3, 130, 4, 128, 128, 64, 29, 4, 7, 0.3),   # 16 * ceil(L / 16) > 128: the persistent path's non-resident candidate
+    # the production widths
+    (17, 40, 5, 512, 512, 256, 62, 8, 7, 0.0),
+    (3, 130, 3, 512, 512, 256, 62, 8, 7, 0.0),  # non-resident
+]
+
+
+def _poisoned_buffers(monkeypatch, s2s):
+    """Every saved / scratch buffer of the host layer starts as all-ones words instead of whatever the allocator hands
+    back (often zeros): a launch path that reads a word nobody wrote -- a sync-region header the harvest reads, say --
+    then fails every time instead of now and then."""
+    monkeypatch.setattr(s2s.nn, "_POISON", True)
+
+
+def _clean_status(s2s):
+    """The context's persistent-launch status after the calls so far: 0, and cleared either way (a set status fails
+    every later call of the process)."""
+    st = s2s.nn.get_context().status(clear=True)
+    assert st == 0, f"context status {st} (1 hand-off timeout, 2 aborted region) after launches that cannot time out"
+
+
+@pytest.mark.parametrize("B,L,T,A,Sc,S,O,M,K,pen", FORCED_CASES)
+@pytest.mark.parametrize("mode", [paths.MODE_STEP, paths.MODE_PERSIST])
+def test_forced_decoder_paths_match_oracle(s2s, monkeypatch, mode, B, L, T, A, Sc, S, O, M, K, pen):
+    """The decoder's two fall-backs at the instantiated widths -- the per-step launches (mode 1) and the 7-seam
+    persistent kernels of attn_persist.inc (mode 2) -- which auto mode reaches only where dec_xcd_plan declines
+    (B > 128, a chunk longer than 64 frames, T > 256), forced with s2s_debug_dec_mode and held to the float64 oracle
+    at the suite's bar, with the path that ran asserted.  A persistent launch keeps its chunks resident while
+    16 * ceil(L / 16) <= 128 workgroups of a tile hold them; longer utterances take the non-resident kernels.
+
+    The persistent kernels take more than 256 registers per lane, one workgroup per CU, so their 128 workgroups per
+    16-row tile are co-resident for two tiles on the 256 CUs: at B > 32 the occupancy query declines both candidates
+    and mode 2 runs the per-step launches (B = 33 here; accepted as either path, like the auto-mode fall-backs, and
+    measured as the per-step one) -- with the sync-region headers that attn_sync_regions still hands to the caller's
+    harvest prepared all the same (they were stale memory: a spurious hand-off timeout status)."""
+    _poisoned_buffers(monkeypatch, s2s)
+    want = paths.STEPS if mode == paths.MODE_STEP else paths.PERSIST if B <= 32 else (paths.PERSIST, paths.STEPS)
+    try:
+        with paths.dec_mode(mode):
+            dec = _check_attention(s2s, B, L, T, A, Sc, S, O, M, K, pen, expect_path=want)
+    finally:
+        _clean_status(s2s)
+    if dec["dec.fwd.path"] == paths.PERSIST:
+        assert dec.count("dec.persist_res") == 2
+        if 16 * ((L + 15) // 16) > 128:
+            paths.took(dec, "dec.persist_res", 0)
+        else:
+            assert dec["dec.persist_res"] in (0, 1)  # (the resident candidate only while the occupancy query admits it)
+
+
+def test_decoder_auto_mode_small_shape_runs_xcd(s2s):
+    """Contrast for the fall-back tests below: with no knob set, a small batch at the small instantiated widths runs the
+    XCD-local decoder.  (A regression that sends everything to the fall-backs fails here first.)"""
+    with paths.dec_mode(paths.MODE_AUTO):
+        _check_attention(s2s, 3, 20, 3, 128, 128, 64, 29, 4, 7, 0.0, expect_path=paths.XCD)
+
+
+# (B, L, T, accepted paths, resident candidate or None): shapes dec_xcd_plan declines, at the small widths
+FALLBACK_CASES = [
+    (3, 1028, 3, (paths.PERSIST,), 0),    # U = 1: 16 chunks of 68 frames > 64; 65 16-frame chunks <= 256: persistent
+    (2, 20, 257, (paths.PERSIST,), 1),    # T > 256 (dec_xcd_dvh stages up to 256 steps)
+    # U = 16, two chunks of 68 frames; 8 tiles x 128 workgroups: persistent only if the occupancy query finds them
+    # co-resident, else the per-step launches
+    (128, 130, 3, (paths.PERSIST, paths.STEPS), None),
+    (129, 8, 2, (paths.PERSIST, paths.STEPS), None),    # U = 17 > 16
+]
+
+
+@pytest.mark.parametrize("B,L,T,accept,res", FALLBACK_CASES)
+def test_decoder_auto_mode_fallbacks_match_oracle(s2s, monkeypatch, B, L, T, accept, res):
+    """Auto mode where the XCD-local plan declines: attn_fwd / attn_bwd_core fall back to the persistent decoder
+    kernels (dec_persist_variant) or, where those are not co-resident, to the per-step launches -- live paths of the
+    default dispatch, against the oracle, with the path asserted not to be the XCD-local one, on poisoned buffers and
+    with the context's status clean afterwards."""
+    _poisoned_buffers(monkeypatch, s2s)
+    try:
+        with paths.dec_mode(paths.MODE_AUTO):
+            dec = _check_attention(s2s, B, L, T, 128, 128, 64, 29, 4, 7, 0.0, expect_path=accept)
+    finally:
+        _clean_status(s2s)
+    print(f"auto-mode fallback B={B} L={L} T={T}: path {dec['dec.fwd.path']} persist_res {dec['dec.persist_res']}")
+    assert dec["dec.fwd.path"] != paths.XCD and dec["dec.bwd.path"] != paths.XCD
+    if res is not None:
+        paths.took(dec, "dec.persist_res", res)
+
+
+# B, L -> the plan dec_xcd_plan makes (U, nchains, XLC, NCH, res), derived by hand from its rules: U = ceil(B / 8),
+# nchains = ceil(B / U), nmax = min(16, 32 // U), XLC = ceil(L / nmax) rounded up to 4, NCH = ceil(L / XLC),
+# res = 2 while XLC <= 32 else 1.  A planner change must edit this table consciously.
+XCD_CHAIN_PLANS = {
+    (40, 50): (5, 8, 12, 5, 2),     # 32 / U not integral, last chunk 2 frames
+    (41, 16): (6, 7, 4, 4, 2),      # fewer than 8 chains with U > 1
+    (56, 37): (7, 8, 12, 4, 2),     # last chunk 1 frame
+    (57, 20): (8, 8, 8, 3, 2),      # last chain one utterance
+    (65, 33): (9, 8, 12, 3, 2),     # last chain two utterances
+    (81, 33): (11, 8, 20, 2, 2),    # nmax = 2
+    (128, 70): (16, 8, 36, 2, 1),   # largest U, streamed level
+}
+
+
+@pytest.mark.parametrize("B,L,local", [(40, 50, 1), (40, 50, 0), (41, 16, 1), (56, 37, 1), (57, 20, 1), (65, 33, 1),
+                                       (81, 33, 1), (128, 70, 1), (128, 70, 0)])
+def test_xcd_decoder_chain_shapes(s2s, B, L, local):
+    """Chain shapes of the XCD-local decoder beyond U = 1 .. 4 and 8: odd U above 3 (32 workgroups per chain do not
+    divide), U = 16, fewer than 8 chains of several utterances, ragged last chains and chunks -- small widths, T = 3,
+    against the oracle, with the launched plan equal to the hand-derived table."""
+    import ctypes
+    from s2s_amd import _lib
+    fn = _lib.lib.s2s_debug_dec_local
+    fn.argtypes = [ctypes.c_int]
+    pen = 0.2 if list(XCD_CHAIN_PLANS).index((B, L)) % 2 else 0.0
+    fn(local)
+    try:
+        with paths.dec_mode(paths.MODE_AUTO):
+            dec = _check_attention(s2s, B, L, 3, 128, 128, 64, 29, 4, 7, pen, expect_path=paths.XCD)
+    finally:
+        fn(1)
+    got = tuple(dec[n] for n in ("dec.U", "dec.nchains", "dec.XLC", "dec.NCH", "dec.res"))
+    assert got == XCD_CHAIN_PLANS[(B, L)], (got, XCD_CHAIN_PLANS[(B, L)])
+    paths.took(dec, "dec.allow_local", local)
+    paths.took(dec, "dec.r4", 0)  # chains of more than 4 utterances: the 16-row products
 
 
 @pytest.mark.parametrize("maxnorm,wd,colnorm,eta", [(1e20, 0.0, False, 0.0), (0.5, 0.0, True, 0.0),

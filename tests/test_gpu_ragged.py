@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import paths
 from oracle import s2s_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -56,11 +57,17 @@ def test_bigru_lengths_match_per_utterance(s2s, monkeypatch, mode, B, L, D, H):
     mod = s2s.BiRNN(cells[0], cells[1]).cuda()
     mod.lengths = lens
     xs = cu(x)
-    y = mod.forward(xs).cpu().numpy()
-    dy = rng.standard_normal(y.shape)
-    mod.zeroGradParameters()
-    dx = mod.backward(xs, cu(dy), 0.5).cpu().numpy()
-    torch.cuda.synchronize()
+    with paths.decisions() as dec:
+        y = mod.forward(xs).cpu().numpy()
+        dy = rng.standard_normal(y.shape)
+        mod.zeroGradParameters()
+        dx = mod.backward(xs, cu(dy), 0.5).cpu().numpy()
+        torch.cuda.synchronize()
+    # the persistent kernels have no H = 32 instantiation: that shape's "persistent" arm is the default dispatch,
+    # which runs the per-step launches there too
+    want = 1 if mode == "persistent" and H == 64 else 0
+    paths.took(dec, "gru.fwd.path", want)
+    paths.took(dec, "gru.bwd.path", want)
     errs = {}
     for i, (W, rev) in enumerate(zip(Ws, [False, True])):
         G = {k: np.zeros_like(v) for k, v in zip(("Wz", "Wr", "Wh"), W)}
@@ -105,11 +112,14 @@ def test_bilstm_lengths_match_per_utterance(s2s, monkeypatch, mode, peep, B, L, 
     mod = s2s.BiRNN(cells[0], cells[1]).cuda()
     mod.lengths = lens
     xs = cu(x)
-    y = mod.forward(xs).cpu().numpy()
-    dy = rng.standard_normal(y.shape)
-    mod.zeroGradParameters()
-    dx = mod.backward(xs, cu(dy), 0.5).cpu().numpy()
-    torch.cuda.synchronize()
+    with paths.decisions() as dec:
+        y = mod.forward(xs).cpu().numpy()
+        dy = rng.standard_normal(y.shape)
+        mod.zeroGradParameters()
+        dx = mod.backward(xs, cu(dy), 0.5).cpu().numpy()
+        torch.cuda.synchronize()
+    paths.took(dec, "lstm.fwd.path", 1 if mode == "persistent" else 0)
+    paths.took(dec, "lstm.bwd.path", 1 if mode == "persistent" else 0)
     errs = {}
     dx_ref = np.zeros_like(x)
     for i, (P, rev) in enumerate(zip(Ps, [False, True])):
@@ -180,14 +190,18 @@ def test_attention_lengths_match_per_utterance(s2s, B, L, T, A, Sc, S, O, M, K, 
     labels = rng.integers(0, O, (B, T)).astype(np.int32)
     att.frame_lengths, att.label_lengths = flen, tlen
     hs = cu(h)
-    logp = att.forward([hs, cu(labels, torch.int32)]).cpu().numpy()
-    alpha = att.alpha().cpu().numpy()
-    gind = att.mono_ind().cpu().numpy().astype(np.float64)
-    dlogp = rng.standard_normal(logp.shape)
-    dlogp[np.arange(T)[None, :] >= tlen[:, None]] = 0.0  # nll_seed's dlogp on padding steps
-    att.zeroGradParameters()
-    dh = att.backward([hs, None], cu(dlogp), 0.5)[0].cpu().numpy()
-    torch.cuda.synchronize()
+    with paths.decisions() as dec:
+        logp = att.forward([hs, cu(labels, torch.int32)]).cpu().numpy()
+        alpha = att.alpha().cpu().numpy()
+        gind = att.mono_ind().cpu().numpy().astype(np.float64)
+        dlogp = rng.standard_normal(logp.shape)
+        dlogp[np.arange(T)[None, :] >= tlen[:, None]] = 0.0  # nll_seed's dlogp on padding steps
+        att.zeroGradParameters()
+        dh = att.backward([hs, None], cu(dlogp), 0.5)[0].cpu().numpy()
+        torch.cuda.synchronize()
+    want = paths.XCD if S in (64, 256) else paths.STEPS  # (as RAGGED_ATT's comment says)
+    paths.took(dec, "dec.fwd.path", want)
+    paths.took(dec, "dec.bwd.path", want)
     G = orc.zeros_like_params(P)
     dhr = np.zeros_like(h)
     errs = {}
