@@ -220,11 +220,22 @@ const int* s2s_attn_maxout_argmax(const s2s_attn_dims* d, const void* saved);
  * out_score (B, may be NULL) its summed log-probability.  Hypotheses finish on eos or at maxseqlength;
  * K in [1, 16].  Blocks until done (it polls for the end of the search).  Content or hybrid attention
  * (alpha_{t-1} carried per hypothesis), GRU or LSTM decoder_recurrent (the cell carried: the reference's
- * hidden {alpha, s, mem}, Attention.lua:360-403), fused decoder_mlp; frame_lengths must be NULL. */
+ * hidden {alpha, s, mem}, Attention.lua:360-403), fused decoder_mlp.
+ * Content attention shares each utterance's Vh and h among its hypotheses: the workspace holds no copy of h, so
+ * h must stay valid until the search has finished.  It also takes a padded batch: with frame_lengths (B),
+ * frames >= L_b of utterance b get no attention weight.  frame_lengths with hybrid attention is an error
+ * (search such an utterance's own frames); label_lengths is ignored. */
 size_t s2s_attn_beam_workspace_bytes(const s2s_attn_dims* d, int K, int maxseqlength);
 int s2s_attn_beam_search(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, const float* h,
                          const float* const* params, int eos, int K, int maxseqlength, int* out, int ldo, int* out_len,
                          float* out_score, void* workspace, size_t workspace_bytes);
+/* The same search with a length limit per utterance: maxseqlengths (device int32, B), each clamped to
+ * [1, maxseqlength] (timit/timit.lua:400 searches every utterance to its own frame count); out, ldo and the
+ * workspace are sized by maxseqlength as above. */
+int s2s_attn_beam_search_ragged(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, const float* h,
+                                const float* const* params, int eos, int K, int maxseqlength,
+                                const int* maxseqlengths, int* out, int ldo, int* out_len, float* out_score,
+                                void* workspace, size_t workspace_bytes);
 /* The same search in stages, for an external decoder_mlp (external_mlp = 1; also usable with the fused one):
  *   s2s_attn_beam_init;  for count = 0 .. maxseqlength: s2s_attn_beam_step(count) -> [run the decoder_mlp on
  *   the (B*K, S+A) rows at s2s_attn_beam_mlp_input -> (B*K, O) log-probabilities] -> s2s_attn_beam_advance(count,
@@ -233,6 +244,10 @@ int s2s_attn_beam_search(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims*
 int s2s_attn_beam_init(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, const float* h,
                        const float* const* params, int eos, int K, int maxseqlength, void* workspace,
                        size_t workspace_bytes);
+/* Between s2s_attn_beam_init and the first step: per-utterance limits as in s2s_attn_beam_search_ragged (without
+ * this call every utterance runs to maxseqlength). */
+int s2s_attn_beam_set_maxlens(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, int K, int maxseqlength,
+                              const int* maxseqlengths, void* workspace);
 int s2s_attn_beam_step(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, const float* const* params, int K,
                        int maxseqlength, int count, void* workspace, size_t workspace_bytes);
 const float* s2s_attn_beam_mlp_input(const s2s_attn_dims* d, int K, int maxseqlength, void* workspace);
@@ -333,6 +348,11 @@ typedef struct {
  * collective on comm_stream.  Buckets in completion order: 0 = the decoder's parameters, then
  * encoder layers numLayers .. 1 (s2s_model_bucket gives each one's slice of the flat buffer). */
 #define S2S_BUCKET_EVENTS 4
+/* S2S_FORWARD_ONLY: the validation pass (timit/timit.lua:368-417 calls autoencoder:forward only): encoder
+ * forward, decoder forward, logp and nll -- no loss seed, no backward, no weight gradients.  grads may be NULL
+ * and is never written; S2S_ZERO_GRADS is ignored; with S2S_BUCKET_EVENTS it is an error.  logp, nll, the
+ * encoder output and the decoder accessors equal a full step's on the same inputs. */
+#define S2S_FORWARD_ONLY 8
 int s2s_model_bucket_count(const s2s_model_dims* d);
 int s2s_model_bucket(const s2s_model_dims* d, int i, size_t* offset, size_t* count);
 int s2s_stream_wait_bucket(s2s_ctx* ctx, s2s_stream_t stream, int i);

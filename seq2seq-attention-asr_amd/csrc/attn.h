@@ -45,6 +45,10 @@ struct AttnDims {
   // forward's merged head launch then also runs the MLP head's backward (do, dm, the Maxout scatter into dU) and
   // attn_bwd_core launches no dec_mlp_head_bwd (attn_head_bwd_fused); attn_bwd_core's dlogp must be this pointer
   const float* dlogp_early = nullptr;
+  // beam search's shared-annotation layout (internal; 0 = off): the rows are the K hypotheses of vh_rows
+  // utterances, Vh is kept once per utterance (vh_rows, L, Sc), and only the per-step forward kernels' buffers
+  // are laid out -- no backward working set, no persistent-kernel granules
+  int vh_rows = 0;
 };
 int set_device_u64(hipStream_t st, unsigned long long* p, unsigned long long v);
 constexpr int kMaxHybK = 8;  // largest hybrid filter served (the reference's fallback model uses 5)
@@ -114,8 +118,12 @@ const float* attn_saved_dropout_mask(const AttnDims& d, const void* saved);
 // (B, ldo >= maxlen + 1) best hypothesis per utterance (tokens, -1 padded), out_len, out_score (its
 // summed log-probability).  Synchronises the stream (stops when every utterance has K finished).
 size_t attn_beam_workspace_bytes(const AttnDims& d, int K, int maxlen);
+// d.flen (content attention only): frames >= L_b of utterance b take no part.  maxlens (device, B, or null):
+// each utterance's own hypothesis length limit, clamped to [1, maxlen].  h must stay valid until the search ends.
 int attn_beam_search(hipStream_t st, const AttnDims& d, const float* h, const AttnParams& P, int eos, int K,
-                     int maxlen, int* out, int ldo, int* out_len, float* out_score, void* ws, size_t ws_bytes);
+                     int maxlen, const int* maxlens, int* out, int ldo, int* out_len, float* out_score, void* ws,
+                     size_t ws_bytes);
+int attn_beam_set_maxlens(hipStream_t st, const AttnDims& d, int K, int maxlen, const int* maxlens, void* ws);
 // the same search in stages (an external decoder_mlp runs between step and advance on beam_mlp_input's
 // (B*K, S+A) rows and hands back (B*K, O) log-probabilities)
 int attn_beam_init(hipStream_t st, const AttnDims& d, const float* h, const AttnParams& P, int eos, int K, int maxlen,

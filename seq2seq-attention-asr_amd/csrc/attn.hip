@@ -81,6 +81,7 @@ struct AttnK {
 
 struct Layout {
   size_t saved, fwd, bwd;
+  bool overlay;  // the beam's shared layout keeps its post-combine buffers inside PC (carve)
 };
 
 // operands of the XCD-local decoder kernels (dec_xcd.inc)
@@ -196,8 +197,9 @@ constexpr int kXlSP = 448, kXlSCP = 192;  // the LSTM kernels' padded S and Sc (
 Layout carve(const AttnDims& d, AttnK* k, char* saved, char* scratch, XArgs* x = nullptr, XLArgs* y = nullptr) {
   const long B = d.B, L = d.L, T = d.T, A = d.A, Sc = d.Sc, S = d.S, O = d.O, M = d.M, Mk = (long)d.M * d.K;
   const long NCH = (d.L + LC - 1) / LC, BT = B * T;
+  const bool beam = d.vh_rows > 0;  // the beam search's shared layout (AttnDims::vh_rows)
   Bump sv{saved, 0, 0};
-  float* Vh = sv.take<float>(B * L * Sc);
+  float* Vh = sv.take<float>((beam ? d.vh_rows : B) * L * Sc);
   float* WS = sv.take<float>(BT * Sc);
   float* E = sv.take<float>(BT * L);
   float* ALPHA = sv.take<float>(BT * L);
@@ -205,15 +207,28 @@ Layout carve(const AttnDims& d, AttnK* k, char* saved, char* scratch, XArgs* x =
   float* IND = sv.take<float>(BT);
   float* C = sv.take<float>(BT * A);
   float* HX = sv.take<float>(BT * 2 * S);
+  const long NG = d.lstm ? 4 : 3;  // gate rows per step: GRU z, r, hh / LSTM i, f, g, o
+  // The beam's shared layout: what a step writes only after dec_f3_combine has consumed the chunk partials PC
+  // (F4 .. the MLP head: RHX, CY, the gates, U, the Maxout and the log-probabilities), and the search reads
+  // before the next step's attention launch refills PC, lives inside PC when it fits there.
+  const size_t ovl_counts[7] = {size_t(BT * 2 * S), size_t(BT * 2 * S), size_t(BT * NG * S), size_t(BT * M),
+                                size_t(BT * M),     size_t(BT * O),     size_t(BT * Mk)};
+  size_t ovl_bytes = 0;
+  for (size_t n : ovl_counts) ovl_bytes = ((ovl_bytes + 255) & ~size_t(255)) + n * sizeof(float);
+  const bool overlay = beam && ovl_bytes <= size_t(B * NCH * A) * sizeof(float);
+  sv.lean = overlay;
   float* RHX = sv.take<float>(BT * 2 * S);
   float* CY = sv.take<float>(BT * 2 * S);
-  const long NG = d.lstm ? 4 : 3;  // gate rows per step: GRU z, r, hh / LSTM i, f, g, o
   float* GSV = sv.take<float>(BT * NG * S);
+  sv.lean = false;
   float* VV = sv.take<float>(BT * (S + A));
+  sv.lean = overlay;
   float* MM = sv.take<float>(BT * M);
   int* AM = sv.take<int>(BT * M);
   float* LOGP = sv.take<float>(BT * O);
+  sv.lean = false;
   float* MASK = d.dropout > 0.f ? sv.take<float>(BT * (S + A)) : nullptr;
+  sv.lean = beam;  // (the XCD-local kernels' operands: the beam steps are per-step launches)
   float* WX = sv.take<float>(3 * S * A);
   float* WXT = sv.take<float>(3 * S * A);
   float* WXD = sv.take<float>(3 * S * S);
@@ -221,6 +236,7 @@ Layout carve(const AttnDims& d, AttnK* k, char* saved, char* scratch, XArgs* x =
   float* XZRT = sv.take<float>(2 * S * S);
   float* XWST = sv.take<float>(S * Sc);
   float* VBAR = sv.take<float>(B * Sc);  // mean Vh row per utterance (computed by the forward)
+  sv.lean = false;
   float* LW = d.lstm ? sv.take<float>(4 * S * 2 * S) : nullptr;
   float* LB = d.lstm ? sv.take<float>(4 * S) : nullptr;
   float* LCS = d.lstm ? sv.take<float>(BT * S) : nullptr;
@@ -230,7 +246,7 @@ Layout carve(const AttnDims& d, AttnK* k, char* saved, char* scratch, XArgs* x =
   const XPlan xpl = dec_xcd_plan(d);
   const long NX = std::max(1, xpl.NCH);
   // the LSTM / hybrid XCD-local kernels' operands (var 3; empty otherwise)
-  const bool v3 = xpl.var == 3;
+  const bool v3 = xpl.var == 3 && !beam;
   const long SP = v3 ? kXlSP : 0, SCP = v3 ? kXlSCP : 0, S4 = v3 ? 4 * S : 0;
   float* lWG = sv.take<float>(4 * SP * SP);
   float* lWXG = sv.take<float>(4 * SP * A);
@@ -243,7 +259,19 @@ Layout carve(const AttnDims& d, AttnK* k, char* saved, char* scratch, XArgs* x =
   float* PM = f.take<float>(B * NCH);
   float* PL = f.take<float>(B * NCH);
   float* PC = f.take<float>(B * NCH * A);
+  f.lean = overlay;
   float* U = f.take<float>(BT * Mk);
+  if (overlay) {
+    Bump o{reinterpret_cast<char*>(PC), 0, 0};
+    RHX = o.take<float>(ovl_counts[0]);
+    CY = o.take<float>(ovl_counts[1]);
+    GSV = o.take<float>(ovl_counts[2]);
+    MM = o.take<float>(ovl_counts[3]);
+    AM = o.take<int>(ovl_counts[4]);
+    LOGP = o.take<float>(ovl_counts[5]);
+    U = o.take<float>(ovl_counts[6]);
+  }
+  f.lean = beam;
   float* WDC = f.take<float>(S * A);
   float* PWDYT = f.take<float>(S * S);
   float* PWDCT = f.take<float>(S * S);
@@ -256,6 +284,7 @@ Layout carve(const AttnDims& d, AttnK* k, char* saved, char* scratch, XArgs* x =
   float* lBQ = f.take<float>(S4);
   float* lKXG = f.take<float>(v3 ? BT * 4 * SP : 0);
   Bump g{scratch, 0, 0};
+  g.lean = beam;
   float* DO = g.take<float>(BT * O);
   float* DU = g.take<float>(BT * Mk);
   float* DV = g.take<float>(BT * (S + A));
@@ -305,7 +334,7 @@ Layout carve(const AttnDims& d, AttnK* k, char* saved, char* scratch, XArgs* x =
   granule_t* lgE = f.take<granule_t>(v3 ? 2 * B * L : 0);
   granule_t* lgA = f.take<granule_t>(v3 ? 2 * B * L : 0);
   unsigned* fcensus = f.take<unsigned>(kXChains * kXWG);
-  const size_t fsync_bytes = f.off - (size_t)(fsync - scratch);
+  const size_t fsync_bytes = fsync ? f.off - (size_t)(fsync - scratch) : 0;
   float* lsS = f.take<float>(BT * SP);
   float* xsS = f.take<float>(BT * S);
   float* xsQ = f.take<float>(BT * S);
@@ -333,7 +362,7 @@ Layout carve(const AttnDims& d, AttnK* k, char* saved, char* scratch, XArgs* x =
   granule_t* lgDWS = g.take<granule_t>(2 * B * SCP);
   granule_t* lgQA = g.take<granule_t>(v3 ? 2 * B * L * HK : 0);
   unsigned* bcensus = g.take<unsigned>(kXChains * kXWG);
-  const size_t bsync_bytes = g.off - (size_t)(bsync - scratch);
+  const size_t bsync_bytes = bsync ? g.off - (size_t)(bsync - scratch) : 0;
   float* lsDG[4];
   for (auto& q : lsDG) q = g.take<float>(BT * SP);
   float* lsDC[2];
@@ -388,7 +417,7 @@ Layout carve(const AttnDims& d, AttnK* k, char* saved, char* scratch, XArgs* x =
     k->fhdr = scratch + hoff;
     k->bhdr = scratch + hoff + 256;
   }
-  return Layout{sv.off + 256, f.off + 256, g.off + 256};
+  return Layout{sv.off + 256, f.off + 256, g.off + 256, overlay};
 }
 
 __device__ __forceinline__ int brow(int b0, int lane, int B) { return min(b0 + (lane & 15), B - 1); }
@@ -2087,7 +2116,98 @@ struct BeamK {
   // (Attention.lua:360-403)
   float *pbeam, *s, *fscore, *alpha, *mem;
   float* mlp_in;  // (R, S + A) decoder_mlp input rows of the current step (external decoder_mlp)
+  int* maxlens;   // (B) each utterance's own hypothesis length limit, in [1, maxlen]
+  // shared-annotation path (beam_f2_shared): the caller's h (B, L, A), kept in the state by beam_init because
+  // the stepwise calls do not pass it again, and the utterances' frame lengths (B, or null)
+  const float** hptr;
+  const int* frames;
 };
+
+constexpr int kBeamMaxK = 16;
+
+// The attention chunk of dec_f2_attn for all active hypotheses of one utterance at once.  grid (NCH, B).
+// Row r = b*K + j (j < nact[b]) of the T = 2 problem scores utterance b's Vh rows against its own ws and sums
+// its own context, but every Vh / h frame row is loaded once per workgroup: the Vh float4 of a lane meets all
+// hypotheses' ws before the next one is fetched, and the context loop's hv[LC] registers are reused per row.
+// Per (row, frame) the sums run in dec_f2_attn's order (lane-strided float4 columns, wave_sum, context in
+// frame order).  Frames l >= L_b score -inf and weigh 0; a chunk wholly past L_b writes PM = -inf, PL = PC = 0.
+template <int WV>
+__global__ __launch_bounds__(64 * WV) void beam_f2_shared(AttnK k, BeamK q) {
+  constexpr int FPW = LC / WV, NT = 64 * WV;
+  __shared__ float sc[kBeamMaxK][LC];
+  __shared__ float pw[kBeamMaxK][LC];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ch = blockIdx.x, b = blockIdx.y;
+  if (q.done[b]) return;
+  const int L = k.L, Sc = k.Sc, A = k.A, K = q.K, NCH = k.NCH;
+  const int na = min(q.nact[b], K);
+  const int Lb = q.frames ? min(q.frames[b], L) : L;
+  const float* we = k.P.we;
+  const float* ws0 = k.WS + ((long)b * K * 2 + 1) * Sc;  // row r's ws_t at ws0 + j * 2 * Sc (t = 1 of T = 2)
+  for (int i = 0; i < FPW; ++i) {
+    const int li = wave * FPW + i, l = ch * LC + li;
+    float part[kBeamMaxK];
+#pragma unroll
+    for (int j = 0; j < kBeamMaxK; ++j) part[j] = 0.f;
+    if (l < Lb) {
+      const float* vh = k.Vh + ((long)b * L + l) * Sc;
+      for (int c4 = lane; c4 < Sc / 4; c4 += 64) {
+        const float4 v = reinterpret_cast<const float4*>(vh)[c4];
+        const float4 e = reinterpret_cast<const float4*>(we)[c4];
+#pragma unroll
+        for (int j = 0; j < kBeamMaxK; ++j) {
+          if (j < na) {
+            const float4 w = reinterpret_cast<const float4*>(ws0 + (long)j * 2 * Sc)[c4];
+            const float4 z = make_float4(w.x + v.x, w.y + v.y, w.z + v.z, w.w + v.w);
+            part[j] += e.x * tanhf(z.x) + e.y * tanhf(z.y) + e.z * tanhf(z.z) + e.w * tanhf(z.w);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kBeamMaxK; ++j) {
+      if (j < na) {
+        const float p = wave_sum(part[j]);
+        if (lane == 0) sc[j][li] = l < Lb ? p : -INFINITY;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < na * LC) {
+    const int j = tid / LC, li = tid - j * LC, l = ch * LC + li;
+    float m = -INFINITY;
+    for (int i = 0; i < LC; ++i) m = fmaxf(m, sc[j][i]);
+    pw[j][li] = l < Lb ? expf(sc[j][li] - m) : 0.f;
+    if (l < L) k.E[((long)(b * K + j) * 2 + 1) * L + l] = sc[j][li];
+    if (li == 0) k.PM[(b * K + j) * NCH + ch] = m;
+  }
+  __syncthreads();
+  if (tid < na) {
+    float s = 0.f;
+    for (int i = 0; i < LC; ++i) s += pw[tid][i];
+    k.PL[(b * K + tid) * NCH + ch] = s;
+  }
+  const float* h = q.hptr[0];
+  const int lend = min(LC, L - ch * LC);
+  for (int a4 = tid; a4 < A / 4; a4 += NT) {
+    float4 hv[LC];
+#pragma unroll
+    for (int i = 0; i < LC; ++i)
+      hv[i] = i < lend ? reinterpret_cast<const float4*>(h + ((long)b * L + ch * LC + i) * A)[a4]
+                       : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int j = 0; j < na; ++j) {
+      float4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int i = 0; i < LC; ++i) {
+        if (i < lend) {
+          const float p = pw[j][i];
+          acc.x += p * hv[i].x; acc.y += p * hv[i].y; acc.z += p * hv[i].z; acc.w += p * hv[i].w;
+        }
+      }
+      reinterpret_cast<float4*>(k.PC + ((long)(b * K + j) * NCH + ch) * A)[a4] = acc;
+    }
+  }
+}
 
 // hypothesis row r = b*K + k gets utterance b's annotations (grid.y = utterance)
 __global__ void beam_rep_h(const float* h, float* hr, int K, long per) {
@@ -2096,8 +2216,9 @@ __global__ void beam_rep_h(const float* h, float* hr, int K, long per) {
     hr[(long)b * K * per + i] = h[(long)b * per + i % per];
 }
 
-__global__ void beam_init(BeamK q) {
+__global__ void beam_init(BeamK q, const float* h) {
   const int R = q.B * q.K;
+  if (blockIdx.x == 0 && threadIdx.x == 0) q.hptr[0] = h;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < R * q.S; i += gridDim.x * blockDim.x) {
     q.s[i] = 0.f;
     if (q.lstm) q.mem[i] = 0.f;
@@ -2113,6 +2234,7 @@ __global__ void beam_init(BeamK q) {
       q.nact[r] = 1;
       q.nfin[r] = 0;
       q.done[r] = 0;
+      q.maxlens[r] = q.maxlen;
     }
   }
 }
@@ -2138,7 +2260,11 @@ __global__ void beam_prep(AttnK k, BeamK q, int par) {
   }
 }
 
-constexpr int kBeamMaxK = 16;
+// each utterance's own limit (s2s_attn_beam_set_maxlens), clamped to [1, maxlen]
+__global__ void beam_set_maxlens(BeamK q, const int* maxlens) {
+  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < q.B; b += gridDim.x * blockDim.x)
+    q.maxlens[b] = min(max(maxlens[b], 1), q.maxlen);
+}
 
 __global__ __launch_bounds__(256) void beam_update(AttnK k, BeamK q, int count) {
   __shared__ float bv[256];
@@ -2151,7 +2277,7 @@ __global__ __launch_bounds__(256) void beam_update(AttnK k, BeamK q, int count) 
   const int b = blockIdx.x, tid = threadIdx.x, K = q.K, O = q.O, S = q.S, R = q.B * K;
   if (q.done[b]) return;
   const int nact = q.nact[b], ncand = nact * O;
-  const int par = count & 1, nxt = par ^ 1;
+  const int par = count & 1, nxt = par ^ 1, maxlen = q.maxlens[b];  // the utterance's own limit
   auto cval = [&](int c) {
     const int i = c / O, j = c - i * O;
     return k.LOGP[((long)(b * K + i) * 2 + 1) * O + j] + q.pbeam[b * K + i];
@@ -2188,7 +2314,7 @@ __global__ __launch_bounds__(256) void beam_update(AttnK k, BeamK q, int count) 
     const int fin = q.nfin[b];
     for (int m = 0; m < K - fin && m < nsel; ++m) {
       const int i = sel[m] / O, j = sel[m] - i * O;
-      if (j == q.eos || (count > 0 && count == q.maxlen)) {
+      if (j == q.eos || (count > 0 && count == maxlen)) {
         fpar[nf] = i; ftok[nf] = j; fsc[nf] = selv[m]; fdst[nf] = fin + nf; ++nf;
       } else {
         npar[nn] = i; ntok[nn] = j; np_[nn] = selv[m]; ++nn;
@@ -2234,7 +2360,7 @@ __global__ __launch_bounds__(256) void beam_update(AttnK k, BeamK q, int count) 
   if (tid == 0) {
     q.nfin[b] += nf;
     q.nact[b] = nn;
-    q.done[b] = (q.nfin[b] >= K || count >= q.maxlen) ? 1 : 0;
+    q.done[b] = (q.nfin[b] >= K || count >= maxlen) ? 1 : 0;
   }
 }
 
@@ -2295,8 +2421,16 @@ __global__ void edit_distance_kernel(int n, const int* a, const int* alen, int l
   out[p] = row[m];
 }
 
+// s2s_debug_beam_replicate(1): content attention also takes the replicated path (A/B arm, tests); a search must
+// run start to end under one setting, since the workspace layout follows it
+std::atomic<int> g_beam_replicate{0};
+// Content attention shares each utterance's Vh and h among its hypotheses (beam_f2_shared); hybrid attention
+// keeps one private copy per hypothesis row (its location features come from the row's own alpha_{t-1})
+bool beam_shared(const AttnDims& d) { return d.hf == 0 && !g_beam_replicate.load(); }
+
 AttnDims beam_dims(const AttnDims& d, int K) {
   AttnDims d2 = d;
+  d2.vh_rows = beam_shared(d) ? d.B : 0;
   d2.B = d.B * K;
   d2.T = 2;
   d2.dropout = 0.f;  // evaluate() mode
@@ -2314,14 +2448,17 @@ BeamLayout beam_layout(const AttnDims& d, int K, int maxlen) {
   const size_t R = (size_t)d.B * K, L1 = (size_t)maxlen + 1;
   auto up = [](size_t x) { return (x + 255) / 256 * 256; };
   BeamLayout l;
+  const bool shared = d2.vh_rows > 0;
   l.hrep = 0;
-  l.saved = up(sizeof(float) * R * d.L * d.A);
+  l.saved = shared ? 0 : up(sizeof(float) * R * d.L * d.A);  // (the shared path reads the caller's h)
   l.scratch = l.saved + up(attn_saved_bytes(d2));
   l.state = l.scratch + up(attn_scratch_bytes(d2));
-  const size_t ints = 3 * (size_t)d.B + R /*yprev*/ + 2 * R * L1 /*hist*/ + 2 * R /*hlen*/ + R * L1 /*fseq*/ +
-                      R /*flen*/ + 2 * R /*lab2*/;
-  const size_t floats = R /*pbeam*/ + 2 * R * d.S /*s*/ + R /*fscore*/ + 2 * R * d.L /*alpha*/ + 2 * R * d.S /*mem*/ +
-                        R * (size_t)(d.S + d.A) /*mlp_in*/;
+  const size_t ints = 2 /*hptr*/ + 4 * (size_t)d.B + R /*yprev*/ + 2 * R * L1 /*hist*/ + 2 * R /*hlen*/ +
+                      R * L1 /*fseq*/ + R /*flen*/ + 2 * R /*lab2*/;
+  // alpha_{t-1} per hypothesis only feeds hybrid attention's location features
+  // (the LSTM cell only with an LSTM decoder)
+  const size_t floats = R /*pbeam*/ + 2 * R * d.S /*s*/ + R /*fscore*/ + (shared ? 0 : 2 * R * d.L) /*alpha*/ +
+                        (d.lstm ? 2 * R * d.S : 0) /*mem*/ + R * (size_t)(d.S + d.A) /*mlp_in*/;
   l.fstate = l.state + up(4 * ints);
   l.total = l.fstate + up(4 * floats);
   return l;
@@ -2335,6 +2472,7 @@ size_t attn_beam_workspace_bytes(const AttnDims& d, int K, int maxlen) { return 
 // the per-hypothesis bookkeeping.  Every stage re-derives the same views from (d, K, maxlen, ws).
 struct BeamView {
   AttnDims d2;
+  bool overlay;
   AttnK k;
   BeamK q;
   float* hrep;
@@ -2345,14 +2483,16 @@ static int beam_view(const AttnDims& d, const AttnParams& P, int eos, int K, int
   S2S_TRY(attn_check_dims(d));
   S2S_REQUIRE(K >= 1 && K <= kBeamMaxK && K <= d.O, "beam search: K must be in [1, 16] and <= outputDepth");
   S2S_REQUIRE(maxlen >= 1 && eos >= 0 && eos < d.O, "beam search: bad eos / maxlen");
-  S2S_REQUIRE(!d.flen, "beam search: frame lengths unsupported (search an utterance's own frames)");
+  S2S_REQUIRE(!d.flen || d.hf == 0,
+              "beam search: frame lengths unsupported with hybrid attention (search an utterance's own frames)");
+  S2S_REQUIRE(!d.flen || beam_shared(d), "beam search: frame lengths need the shared-annotation path");
   const BeamLayout bl = beam_layout(d, K, maxlen);
   S2S_REQUIRE(ws && ws_bytes >= bl.total, "beam search: workspace too small");
   v.d2 = beam_dims(d, K);
   char* base = static_cast<char*>(ws);
   v.hrep = reinterpret_cast<float*>(base + bl.hrep);
   v.k = AttnK{};
-  carve(v.d2, &v.k, base + bl.saved, base + bl.scratch);
+  v.overlay = carve(v.d2, &v.k, base + bl.saved, base + bl.scratch).overlay;
   const int B = d.B, R = B * K, S = d.S, L1 = maxlen + 1;
   BeamK& q = v.q;
   q = BeamK{};
@@ -2360,6 +2500,9 @@ static int beam_view(const AttnDims& d, const AttnParams& P, int eos, int K, int
   q.hyb = d.hf > 0 ? 1 : 0;
   q.lstm = d.lstm ? 1 : 0;
   int* ip = reinterpret_cast<int*>(base + bl.state);
+  q.hptr = reinterpret_cast<const float**>(ip); ip += 2;  // (256-byte aligned: first in the region)
+  q.frames = d.flen;
+  q.maxlens = ip; ip += B;
   q.nact = ip; ip += B;
   q.nfin = ip; ip += B;
   q.done = ip; ip += B;
@@ -2373,8 +2516,8 @@ static int beam_view(const AttnDims& d, const AttnParams& P, int eos, int K, int
   q.pbeam = fp; fp += R;
   q.s = fp; fp += 2L * R * S;
   q.fscore = fp; fp += R;
-  q.alpha = fp; fp += 2L * R * d.L;
-  q.mem = fp; fp += 2L * R * S;
+  q.alpha = fp; fp += v.d2.vh_rows > 0 ? 0 : 2L * R * d.L;
+  q.mem = fp; fp += d.lstm ? 2L * R * S : 0;
   q.mlp_in = fp;
   v.k.P = P;
   v.k.h = v.hrep;
@@ -2390,12 +2533,32 @@ int attn_beam_init(hipStream_t st, const AttnDims& d, const float* h, const Attn
   BeamView v;
   S2S_TRY(beam_view(d, P, eos, K, maxlen, ws, ws_bytes, v));
   const int B = d.B, R = B * K, L = d.L;
-  // annotations and Vh once per hypothesis row (Attention.lua:356-357: vh = Vh:forward(annotations))
-  hipLaunchKernelGGL(beam_rep_h, dim3(64, B), dim3(256), 0, st, h, v.hrep, K, (long)L * d.A);
-  S2S_TRY(gemm1(st, false, true, R * L, d.Sc, d.A, 1.f, v.hrep, d.A, P.V, d.A, 0.f, v.k.Vh, d.Sc, nullptr, v.gws));
-  hipLaunchKernelGGL(beam_init, dim3(64), dim3(256), 0, st, v.q);
+  const bool shared = v.d2.vh_rows > 0;
+  decide("beam.attn.path", shared ? 1 : 0);  // 1: Vh / h once per utterance (beam_f2_shared), 0: per hypothesis row
+  decide("beam.layout.overlay", v.overlay ? 1 : 0);
+  if (shared) {
+    // Vh once per utterance (Attention.lua:356-357: vh = Vh:forward(annotations)); the steps read the caller's h
+    S2S_TRY(gemm1(st, false, true, B * L, d.Sc, d.A, 1.f, h, d.A, P.V, d.A, 0.f, v.k.Vh, d.Sc, nullptr, v.gws));
+  } else {
+    // annotations and Vh once per hypothesis row
+    hipLaunchKernelGGL(beam_rep_h, dim3(64, B), dim3(256), 0, st, h, v.hrep, K, (long)L * d.A);
+    S2S_TRY(gemm1(st, false, true, R * L, d.Sc, d.A, 1.f, v.hrep, d.A, P.V, d.A, 0.f, v.k.Vh, d.Sc, nullptr, v.gws));
+  }
+  hipLaunchKernelGGL(beam_init, dim3(64), dim3(256), 0, st, v.q, h);
   if (d.hf > 0) hipLaunchKernelGGL(dec_hyb_fold, dim3((d.Sc + 255) / 256), dim3(256), 0, st, v.k);
   if (d.lstm) hipLaunchKernelGGL(dec_lstm_pack, dim3(256), dim3(256), 0, st, v.k);
+  S2S_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// per-utterance limits (device, B) in place of maxlen for every utterance, between init and the first step
+// (timit.lua:400 searches each utterance to its own frame count)
+int attn_beam_set_maxlens(hipStream_t st, const AttnDims& d, int K, int maxlen, const int* maxlens, void* ws) {
+  BeamView v;
+  AttnParams P{};
+  S2S_TRY(beam_view(d, P, 0, K, maxlen, ws, beam_layout(d, K, maxlen).total, v));
+  S2S_REQUIRE(maxlens, "beam search: null maxseqlengths");
+  hipLaunchKernelGGL(beam_set_maxlens, dim3((d.B + 255) / 256), dim3(256), 0, st, v.q, maxlens);
   S2S_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -2410,7 +2573,13 @@ int attn_beam_step(hipStream_t st, const AttnDims& d, const AttnParams& P, int K
   const int R = d.B * K, S = d.S, bt = (R + 15) / 16, rows = 2 * R;
   hipLaunchKernelGGL(beam_prep, dim3(64), dim3(256), 0, st, k, v.q, count & 1);
   hipLaunchKernelGGL(dec_f1_ws, dim3(d.Sc / 16, bt), dim3(256), 0, st, k);
-  hipLaunchKernelGGL(dec_f2_attn<8>, dim3(k.NCH, R), dim3(512), 0, st, k);
+  const bool shared = v.d2.vh_rows > 0;
+  decide("beam.attn.path", shared ? 1 : 0);
+  decide("beam.layout.overlay", v.overlay ? 1 : 0);  // the step's post-combine buffers live inside PC (carve)
+  // 16 waves, one frame each: a wave scores its frame for up to K hypotheses in turn, so the serial chain per
+  // launch is K frames' worth where dec_f2_attn<8>'s is 2 (the wave count does not change a bit of the results)
+  if (shared) hipLaunchKernelGGL(beam_f2_shared<16>, dim3(k.NCH, d.B), dim3(1024), 0, st, k, v.q);
+  else hipLaunchKernelGGL(dec_f2_attn<8>, dim3(k.NCH, R), dim3(512), 0, st, k);
   hipLaunchKernelGGL(dec_f3_combine, dim3(R), dim3(256), 0, st, k);
   hipLaunchKernelGGL(dec_f4_cin, dim3(S / 16, bt), dim3(256), 0, st, k);
   hipLaunchKernelGGL(dec_f5_d, dim3(S / 16, bt), dim3(256), 0, st, k);
@@ -2492,10 +2661,12 @@ int attn_beam_finished(hipStream_t st, const AttnDims& d, int K, int maxlen, voi
 }
 
 int attn_beam_search(hipStream_t st, const AttnDims& d, const float* h, const AttnParams& P, int eos, int K,
-                     int maxlen, int* out, int ldo, int* out_len, float* out_score, void* ws, size_t ws_bytes) {
+                     int maxlen, const int* maxlens, int* out, int ldo, int* out_len, float* out_score, void* ws,
+                     size_t ws_bytes) {
   S2S_REQUIRE(!d.ext, "beam search: an external decoder_mlp runs through the stepwise calls");
   S2S_REQUIRE(ldo >= maxlen + 1, "beam search: ldo < maxseqlength + 1");
   S2S_TRY(attn_beam_init(st, d, h, P, eos, K, maxlen, ws, ws_bytes));
+  if (maxlens) S2S_TRY(attn_beam_set_maxlens(st, d, K, maxlen, maxlens, ws));
   for (int count = 0; count <= maxlen; ++count) {
     S2S_TRY(attn_beam_step(st, d, P, K, maxlen, count, ws, ws_bytes));
     S2S_TRY(attn_beam_advance(st, d, eos, K, maxlen, count, nullptr, ws, ws_bytes));
@@ -2532,6 +2703,8 @@ int nll_seed(hipStream_t st, int B, int T, int O, const float* logp, const int* 
 // dec_xcd.inc (tools/xdec_stamps.py, tools/xdec_substamps.py); nullptr turns it off.
 // diagnostic: 0 forces write-through (sc1) hand-offs in every XCD-local decoder chain
 extern "C" void s2s_debug_dec_local(int allow) { s2s::g_dec_allow_local = allow; }
+// diagnostic: 1 sends content attention's beam search down the replicated path too (A/B arm; set between searches)
+extern "C" void s2s_debug_beam_replicate(int on) { s2s::g_beam_replicate = on ? 1 : 0; }
 extern "C" void s2s_debug_merge_alpha_head(int on) { s2s::g_merge_alpha_head = on; }
 // diagnostic: the merged MLP head sums the MLP GEMM's split-K slabs (1) or a reduce launch runs in front of it (0)
 extern "C" void s2s_debug_head_sums_slabs(int on) { s2s::g_head_sums_slabs = on; }

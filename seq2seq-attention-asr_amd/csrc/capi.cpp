@@ -403,8 +403,28 @@ int s2s_attn_beam_search(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims*
   S2S_REQUIRE(d && h && out && out_len && workspace, "beam search: null argument");
   AttnParams ap{};
   S2S_TRY(beam_params(d, params, ap));
-  return attn_beam_search(static_cast<hipStream_t>(stream), to_attn(d), h, ap, eos, K, maxseqlength, out, ldo,
-                          out_len, out_score, workspace, workspace_bytes);
+  return attn_beam_search(static_cast<hipStream_t>(stream), to_attn(d), h, ap, eos, K, maxseqlength, nullptr, out,
+                          ldo, out_len, out_score, workspace, workspace_bytes);
+}
+
+int s2s_attn_beam_search_ragged(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, const float* h,
+                                const float* const* params, int eos, int K, int maxseqlength,
+                                const int* maxseqlengths, int* out, int ldo, int* out_len, float* out_score,
+                                void* workspace, size_t workspace_bytes) {
+  S2S_TRY(set_device(ctx));
+  S2S_REQUIRE(d && h && out && out_len && workspace, "beam search: null argument");
+  AttnParams ap{};
+  S2S_TRY(beam_params(d, params, ap));
+  return attn_beam_search(static_cast<hipStream_t>(stream), to_attn(d), h, ap, eos, K, maxseqlength, maxseqlengths,
+                          out, ldo, out_len, out_score, workspace, workspace_bytes);
+}
+
+int s2s_attn_beam_set_maxlens(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, int K, int maxseqlength,
+                              const int* maxseqlengths, void* workspace) {
+  S2S_TRY(set_device(ctx));
+  S2S_REQUIRE(d && workspace && maxseqlengths, "beam search: null argument");
+  return attn_beam_set_maxlens(static_cast<hipStream_t>(stream), to_attn(d), K, maxseqlength, maxseqlengths,
+                               workspace);
 }
 
 int s2s_attn_beam_init(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, const float* h,

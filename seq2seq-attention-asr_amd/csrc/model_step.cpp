@@ -143,7 +143,10 @@ int model_step_impl(hipStream_t st, hipStream_t side, hipEvent_t* ev, hipEvent_t
   io0.B = d->B;
   io0.H = layers[0].H;
   const bool head_fused = g_sync_handover && gru_layer_persistent(io0);
-  const bool head_seed = head_fused && split;                               // dlogp in the head
+  // S2S_FORWARD_ONLY: encoder and decoder forward and the reported nll -- no loss seed, no backward, no gradient
+  // write (grads may be null), so none of the head's fused backward pieces either
+  const bool fwd_only = (flags & S2S_FORWARD_ONLY) != 0;
+  const bool head_seed = head_fused && split && !fwd_only;                  // dlogp in the head
   const bool head_zero = head_seed && (flags & S2S_ZERO_GRADS);            // zeroing in the head
   // the side stream forks at the step's top (ev[13]).  Measured and rejected: forking after the head, or
   // creating the side branch's nodes after layer 1's launch (the decoder prologue then starts after layer 1 holds
@@ -152,7 +155,7 @@ int model_step_impl(hipStream_t st, hipStream_t side, hipEvent_t* ev, hipEvent_t
     S2S_CHECK_HIP(hipEventRecord(ev[13], st));
     S2S_CHECK_HIP(hipStreamWaitEvent(side, ev[13], 0));
   }
-  if ((flags & S2S_ZERO_GRADS) && !head_zero)
+  if ((flags & S2S_ZERO_GRADS) && !head_zero && !fwd_only)
     S2S_TRY(zero_async(split ? side : st, grads, sizeof(float) * (size_t)nparams));
   const int B = d->B, L = d->L, T = d->T, O = d->outputDepth;
   const int nl = (int)layers.size();
@@ -167,7 +170,7 @@ int model_step_impl(hipStream_t st, hipStream_t side, hipEvent_t* ev, hipEvent_t
   float** gp = reinterpret_cast<float**>(&ag);
   for (int i = 0; i < S2S_ATTN_NPARAMS; ++i) {
     pp[i] = P(dec_slot(nl, i));
-    gp[i] = G(dec_slot(nl, i));
+    gp[i] = grads ? G(dec_slot(nl, i)) : nullptr;
   }
   // layer-1 input padded to a multiple of 32 columns: its GEMMs then run on aligned full tiles
   const float* x0 = x;
@@ -237,11 +240,20 @@ int model_step_impl(hipStream_t st, hipStream_t side, hipEvent_t* ev, hipEvent_t
     }
     else
       S2S_TRY(gru_layers_pack(st, ios.data(), w.pack.data(), nl, defer_pack ? &deferred : nullptr));
+    if (fwd_only && defer_pack) {  // the deferred jobs' transposes (UhT, UzrT) serve only the BPTT launches
+      int n = 0;
+      for (int i = 0; i < deferred.n; ++i) {
+        GruPackJob job = deferred.j[i];
+        job.UhT = job.UzrT = nullptr;
+        if (job.Uzr || job.Uh || job.Wx) deferred.j[n++] = job;
+      }
+      deferred.n = n;
+    }
   }
   // decoder parameter folds + dlogp = -labelmask (params and labels only): on the side stream, joined before the
   // decoder (the persistent GRU launches hold every CU, so it runs in their gaps); inline without a side stream
   if (split) {
-    if (!head_seed)  // dlogp = -labelmask
+    if (!head_seed && !fwd_only)  // dlogp = -labelmask
       S2S_TRY(nll_seed(side, B, T, O, nullptr, labels, 0, nullptr, w.dlogp, d->label_lengths));
     S2S_TRY(attn_fwd_prologue(side, ad, labels, ap, w.attn_saved, w.attn_scratch));
     S2S_CHECK_HIP(hipEventRecord(ev[14], side));
@@ -277,7 +289,8 @@ int model_step_impl(hipStream_t st, hipStream_t side, hipEvent_t* ev, hipEvent_t
   for (int l = 0; l < nl; ++l) {
     GruLayerIO io = layer_io(l);
     const GruLayerIO next = layer_io(l + 1 < nl ? l + 1 : nl - 1);
-    hand_over(io, true, &next);
+    // (the last forward launch prepares the first backward launch's sync region -- when there is a backward)
+    hand_over(io, true, (fwd_only && l + 1 == nl) ? nullptr : &next);
     if (l == 0 && defer_pack) io.pack_jobs = &deferred;
     S2S_TRY(gru_layer_fwd(st, io, w.scratch, w.scratch_bytes));
   }
@@ -288,109 +301,111 @@ int model_step_impl(hipStream_t st, hipStream_t side, hipEvent_t* ev, hipEvent_t
                    nullptr, nullptr));
   // ---- loss seed: dlogp = -labelmask needs only the labels (computed beside the encoder when split);
   // the reported nll (timit.lua:268-272) is computed on the side stream at the end of the step
-  if (!split)
-    S2S_TRY(nll_seed(st, B, T, O, lp, labels, (flags & S2S_NORMALIZE_NLL) ? 1 : 0, nll ? nll : w.nll, w.dlogp,
-                     d->label_lengths));
-  // ---- decoder backward -> dh
-  float* dYcur = w.dY0;
-  float* dYnext = w.dY1;
-  // the decoder's dh (context term + dVh V) is produced by the top layer's BPTT launch itself when it can
-  // (gru_layer_dy_fused), otherwise by GEMMs in front of it
-  AttnDhTerms dht{};
-  S2S_TRY(attn_bwd_core(st, ad, w.Y[nl - 1], labels, ap, w.attn_saved, w.dlogp, dYcur, 0, w.attn_scratch,
-                        w.attn_scratch_bytes, nullptr, nullptr, g_fuse_dh ? &dht : nullptr));
-  // the decoder's weight gradients beside the top BPTT (side stream).  (Creating their nodes after the top BPTT's
-  // launch measured 3.167 -> 3.680 ms: the replayed graph then ran the whole side branch after the last BPTT.)
-  if (split) {
-    S2S_CHECK_HIP(hipEventRecord(ev[0], st));
-    S2S_CHECK_HIP(hipStreamWaitEvent(side, ev[0], 0));
-  }
-  S2S_TRY(attn_bwd_wgrad(split ? side : st, ad, w.Y[nl - 1], labels, ap, w.attn_saved, ag, scale, w.attn_scratch));
-  S2S_TRY(mark_bucket(bev, 0, split ? side : st));
-  // the reported nll (timit.lua:268-272) beside the encoder BPTT
-  if (split)
-    S2S_TRY(nll_seed(side, B, T, O, lp, labels, (flags & S2S_NORMALIZE_NLL) ? 1 : 0, nll ? nll : w.nll, nullptr,
-                     d->label_lengths));
-  // ---- encoder backward.  Layer l's weight-gradient GEMMs (side stream) wait for an event recorded between layer
-  // l-1's BPTT sync prep and its launch, so the persistent BPTT is dispatched before the GEMM's workgroups take the
-  // CUs (forked right after layer l's own BPTT, the replayed graph started the GEMM first and layers 2 and 1's BPTT
-  // ran 590-618 us instead of 533-540 us, profiles/r01)
-  const bool defer = split;
-  int pending = -1;  // layer whose weight gradients wait for the next BPTT's sync prep
-  auto issue_wgrad = [&](int l) -> int {
-    const GruLayerIO io = layer_io(l);
-    GruLayerGrad gr = layer_grad(l, nullptr);
-    gr.scale = scale;
-    S2S_TRY(gru_layer_wgrad(split ? side : st, io, gr, w.dA[l], w.gws_side));
-    S2S_TRY(mark_bucket(bev, nl - l, split ? side : st));
-    return 0;
-  };
-  for (int l = nl - 1; l >= 0; --l) {
-    const int H = layers[l].H;
-    GruLayerIO io = layer_io(l);
-    const GruLayerIO next = layer_io(l > 0 ? l - 1 : 0);
-    hand_over(io, false, l > 0 ? &next : nullptr);
-    GruLayerGrad gr = layer_grad(l, dYcur);
-    // this layer's dX is the dy of the layer below: produced inside that layer's BPTT launch (or by one
-    // GEMM in front of it), so the critical path has no GEMM between two BPTT launches
-    gr.dx = nullptr;
-    if (l == nl - 1 && dht.dvh) {  // dy = dh = sum_t alpha dc + dVh V, in-launch
-      gr.ydA = dht.dvh;
-      gr.yldA = dht.Sc;
-      gr.yK = dht.Sc;
-      gr.yN = dht.A;
-      gr.yWx = dht.V;
-      gr.yldw = dht.A;
-      gr.yalpha = dht.alpha;
-      gr.ydc = dht.dc;
-      gr.yT = dht.T;
-      if (dht.A != 2 * H || !gru_layer_dy_fused(io, gr)) {
-        gr = layer_grad(l, dYcur);
-        S2S_TRY(attn_dh_gemms(st, dht, dYcur, 0));
-      }
+  if (!split || fwd_only)
+    S2S_TRY(nll_seed(st, B, T, O, lp, labels, (flags & S2S_NORMALIZE_NLL) ? 1 : 0, nll ? nll : w.nll,
+                     fwd_only ? nullptr : w.dlogp, d->label_lengths));
+  if (!fwd_only) {
+    // ---- decoder backward -> dh
+    float* dYcur = w.dY0;
+    float* dYnext = w.dY1;
+    // the decoder's dh (context term + dVh V) is produced by the top layer's BPTT launch itself when it can
+    // (gru_layer_dy_fused), otherwise by GEMMs in front of it
+    AttnDhTerms dht{};
+    S2S_TRY(attn_bwd_core(st, ad, w.Y[nl - 1], labels, ap, w.attn_saved, w.dlogp, dYcur, 0, w.attn_scratch,
+                          w.attn_scratch_bytes, nullptr, nullptr, g_fuse_dh ? &dht : nullptr));
+    // the decoder's weight gradients beside the top BPTT (side stream).  (Creating their nodes after the top BPTT's
+    // launch measured 3.167 -> 3.680 ms: the replayed graph then ran the whole side branch after the last BPTT.)
+    if (split) {
+      S2S_CHECK_HIP(hipEventRecord(ev[0], st));
+      S2S_CHECK_HIP(hipStreamWaitEvent(side, ev[0], 0));
     }
-    if (l + 1 < nl) {
-      const GruLayerIO up = layer_io(l + 1);
-      gr.ydA = w.dA[l + 1];
-      gr.yldA = 3L * up.ndir * up.H;
-      gr.yK = 3 * up.ndir * up.H;
-      gr.yN = up.D;
-      gr.yWx = gru_layer_packed_wx(up, &gr.yldw);
-      S2S_REQUIRE(gr.yWx != nullptr && up.ldx == 2L * H, "model step: dX of layer above needs packed weights");
-    }
-    gr.scale = scale;
-    // the first layer's weight gradients inside its BPTT launch: nothing behind the step's last recurrence
-    const bool wg_in = l == 0 && g_bptt_wgrad && gru_layer_wgrad_fused(io);
-    if (wg_in) {
-      gr.wgrad = 1;
-      gr.wpart = w.wpart;
-    }
-    if (l == 0) decide("step.bptt_wgrad_in", wg_in);
-    if (l == nl - 1) decide("step.fuse_dh", gr.yalpha != nullptr);  // the decoder's dh inside the top BPTT launch
-    if (defer && pending >= 0) gr.prep_event = ev[1 + pending];
-    S2S_TRY(gru_layer_bwd_core(st, io, gr, w.dA[l], w.scratch, w.scratch_bytes));
-    if (defer) {
-      if (pending >= 0) {  // the layer above: after this BPTT's dispatch point
-        S2S_CHECK_HIP(hipStreamWaitEvent(side, ev[1 + pending], 0));
-        S2S_TRY(issue_wgrad(pending));
-      }
-      pending = l;
-      if (l == 0 && wg_in) {
-        S2S_TRY(mark_bucket(bev, nl, st));
-      } else if (l == 0) {  // the last BPTT: nothing left to dispatch ahead of layer 1's GEMMs
-        S2S_TRY(fork_to(st, side, ev[1 + l]));
-        S2S_TRY(issue_wgrad(l));
-      }
-    } else if (wg_in) {
-      S2S_TRY(mark_bucket(bev, nl - l, st));
-    } else {
-      if (split) S2S_TRY(fork_to(st, side, ev[1 + l]));
+    S2S_TRY(attn_bwd_wgrad(split ? side : st, ad, w.Y[nl - 1], labels, ap, w.attn_saved, ag, scale, w.attn_scratch));
+    S2S_TRY(mark_bucket(bev, 0, split ? side : st));
+    // the reported nll (timit.lua:268-272) beside the encoder BPTT
+    if (split)
+      S2S_TRY(nll_seed(side, B, T, O, lp, labels, (flags & S2S_NORMALIZE_NLL) ? 1 : 0, nll ? nll : w.nll, nullptr,
+                       d->label_lengths));
+    // ---- encoder backward.  Layer l's weight-gradient GEMMs (side stream) wait for an event recorded between layer
+    // l-1's BPTT sync prep and its launch, so the persistent BPTT is dispatched before the GEMM's workgroups take the
+    // CUs (forked right after layer l's own BPTT, the replayed graph started the GEMM first and layers 2 and 1's BPTT
+    // ran 590-618 us instead of 533-540 us, profiles/r01)
+    const bool defer = split;
+    int pending = -1;  // layer whose weight gradients wait for the next BPTT's sync prep
+    auto issue_wgrad = [&](int l) -> int {
+      const GruLayerIO io = layer_io(l);
+      GruLayerGrad gr = layer_grad(l, nullptr);
+      gr.scale = scale;
       S2S_TRY(gru_layer_wgrad(split ? side : st, io, gr, w.dA[l], w.gws_side));
       S2S_TRY(mark_bucket(bev, nl - l, split ? side : st));
+      return 0;
+    };
+    for (int l = nl - 1; l >= 0; --l) {
+      const int H = layers[l].H;
+      GruLayerIO io = layer_io(l);
+      const GruLayerIO next = layer_io(l > 0 ? l - 1 : 0);
+      hand_over(io, false, l > 0 ? &next : nullptr);
+      GruLayerGrad gr = layer_grad(l, dYcur);
+      // this layer's dX is the dy of the layer below: produced inside that layer's BPTT launch (or by one
+      // GEMM in front of it), so the critical path has no GEMM between two BPTT launches
+      gr.dx = nullptr;
+      if (l == nl - 1 && dht.dvh) {  // dy = dh = sum_t alpha dc + dVh V, in-launch
+        gr.ydA = dht.dvh;
+        gr.yldA = dht.Sc;
+        gr.yK = dht.Sc;
+        gr.yN = dht.A;
+        gr.yWx = dht.V;
+        gr.yldw = dht.A;
+        gr.yalpha = dht.alpha;
+        gr.ydc = dht.dc;
+        gr.yT = dht.T;
+        if (dht.A != 2 * H || !gru_layer_dy_fused(io, gr)) {
+          gr = layer_grad(l, dYcur);
+          S2S_TRY(attn_dh_gemms(st, dht, dYcur, 0));
+        }
+      }
+      if (l + 1 < nl) {
+        const GruLayerIO up = layer_io(l + 1);
+        gr.ydA = w.dA[l + 1];
+        gr.yldA = 3L * up.ndir * up.H;
+        gr.yK = 3 * up.ndir * up.H;
+        gr.yN = up.D;
+        gr.yWx = gru_layer_packed_wx(up, &gr.yldw);
+        S2S_REQUIRE(gr.yWx != nullptr && up.ldx == 2L * H, "model step: dX of layer above needs packed weights");
+      }
+      gr.scale = scale;
+      // the first layer's weight gradients inside its BPTT launch: nothing behind the step's last recurrence
+      const bool wg_in = l == 0 && g_bptt_wgrad && gru_layer_wgrad_fused(io);
+      if (wg_in) {
+        gr.wgrad = 1;
+        gr.wpart = w.wpart;
+      }
+      if (l == 0) decide("step.bptt_wgrad_in", wg_in);
+      if (l == nl - 1) decide("step.fuse_dh", gr.yalpha != nullptr);  // the decoder's dh inside the top BPTT launch
+      if (defer && pending >= 0) gr.prep_event = ev[1 + pending];
+      S2S_TRY(gru_layer_bwd_core(st, io, gr, w.dA[l], w.scratch, w.scratch_bytes));
+      if (defer) {
+        if (pending >= 0) {  // the layer above: after this BPTT's dispatch point
+          S2S_CHECK_HIP(hipStreamWaitEvent(side, ev[1 + pending], 0));
+          S2S_TRY(issue_wgrad(pending));
+        }
+        pending = l;
+        if (l == 0 && wg_in) {
+          S2S_TRY(mark_bucket(bev, nl, st));
+        } else if (l == 0) {  // the last BPTT: nothing left to dispatch ahead of layer 1's GEMMs
+          S2S_TRY(fork_to(st, side, ev[1 + l]));
+          S2S_TRY(issue_wgrad(l));
+        }
+      } else if (wg_in) {
+        S2S_TRY(mark_bucket(bev, nl - l, st));
+      } else {
+        if (split) S2S_TRY(fork_to(st, side, ev[1 + l]));
+        S2S_TRY(gru_layer_wgrad(split ? side : st, io, gr, w.dA[l], w.gws_side));
+        S2S_TRY(mark_bucket(bev, nl - l, split ? side : st));
+      }
+      float* tmp = dYcur;
+      dYcur = dYnext;
+      dYnext = tmp;
     }
-    float* tmp = dYcur;
-    dYcur = dYnext;
-    dYnext = tmp;
   }
   // failure words of every sync region the step's persistent launches used -> the context's status (handoff.h),
   // on the main stream after the last BPTT (beside the side stream's weight-gradient tail)
@@ -489,7 +504,10 @@ int s2s_model_step(s2s_ctx* ctx, s2s_stream_t stream, const s2s_model_dims* d, c
   // mode), where the big GEMM's staging buffer could not be grown
   set_gemm_stage(nullptr);
   S2S_TRY(check_model_dims(d));
-  S2S_REQUIRE(params && grads && x && labels && workspace, "model: null argument");
+  S2S_REQUIRE(params && x && labels && workspace, "model: null argument");
+  S2S_REQUIRE(grads || (flags & S2S_FORWARD_ONLY), "model: null gradients (only S2S_FORWARD_ONLY runs without)");
+  S2S_REQUIRE(!(flags & S2S_FORWARD_ONLY) || !(flags & S2S_BUCKET_EVENTS),
+              "model: S2S_FORWARD_ONLY with S2S_BUCKET_EVENTS (a forward-only step finishes no gradient bucket)");
   S2S_REQUIRE(workspace_bytes >= model_ws(d, nullptr).total, "model: workspace too small");
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipEvent_t* bev = nullptr;

@@ -285,9 +285,11 @@ struct Bump {
   char* base;
   size_t off;
   size_t cap;
+  bool lean = false;  // while set, a take is empty and returns null (a layout that leaves a family of buffers out)
   template <class T>
   T* take(size_t n) {
     size_t a = (off + 255) & ~size_t(255);
+    if (lean) return nullptr;
     T* p = reinterpret_cast<T*>(base ? base + a : nullptr);
     off = a + n * sizeof(T);
     return p;

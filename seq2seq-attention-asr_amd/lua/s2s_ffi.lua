@@ -48,7 +48,9 @@ const float* s2s_attn_dropout_mask(const s2s_attn_dims* d, const void* saved);
 const int* s2s_attn_maxout_argmax(const s2s_attn_dims* d, const void* saved);
 size_t s2s_attn_beam_workspace_bytes(const s2s_attn_dims* d, int K, int maxseqlength);
 int s2s_attn_beam_search(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, const float* h, const float* const* params, int eos, int K, int maxseqlength, int* out, int ldo, int* out_len, float* out_score, void* workspace, size_t workspace_bytes);
+int s2s_attn_beam_search_ragged(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, const float* h, const float* const* params, int eos, int K, int maxseqlength, const int* maxseqlengths, int* out, int ldo, int* out_len, float* out_score, void* workspace, size_t workspace_bytes);
 int s2s_attn_beam_init(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, const float* h, const float* const* params, int eos, int K, int maxseqlength, void* workspace, size_t workspace_bytes);
+int s2s_attn_beam_set_maxlens(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, int K, int maxseqlength, const int* maxseqlengths, void* workspace);
 int s2s_attn_beam_step(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, const float* const* params, int K, int maxseqlength, int count, void* workspace, size_t workspace_bytes);
 const float* s2s_attn_beam_mlp_input(const s2s_attn_dims* d, int K, int maxseqlength, void* workspace);
 int s2s_attn_beam_advance(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, int eos, int K, int maxseqlength, int count, const float* logp, void* workspace, size_t workspace_bytes);
@@ -124,6 +126,7 @@ M.S2S_ATTN_NPARAMS_LSTM = 36
 M.S2S_ZERO_GRADS = 1
 M.S2S_NORMALIZE_NLL = 2
 M.S2S_BUCKET_EVENTS = 4
+M.S2S_FORWARD_ONLY = 8
 M.S2S_UNIQUE_ID_BYTES = 128
 -- END GENERATED CONSTANTS
 

@@ -106,8 +106,11 @@ SIGNATURES = [
     ("s2s_attn_beam_workspace_bytes", c_size_t, [P(s2s_attn_dims), c_int, c_int]),
     ("s2s_attn_beam_search", c_int, [c_void_p, c_void_p, P(s2s_attn_dims), c_void_p, c_void_p, c_int, c_int, c_int,
                                      c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t]),
+    ("s2s_attn_beam_search_ragged", c_int, [c_void_p, c_void_p, P(s2s_attn_dims), c_void_p, c_void_p, c_int, c_int,
+                                            c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t]),
     ("s2s_attn_beam_init", c_int, [c_void_p, c_void_p, P(s2s_attn_dims), c_void_p, c_void_p, c_int, c_int, c_int,
                                    c_void_p, c_size_t]),
+    ("s2s_attn_beam_set_maxlens", c_int, [c_void_p, c_void_p, P(s2s_attn_dims), c_int, c_int, c_void_p, c_void_p]),
     ("s2s_attn_beam_step", c_int, [c_void_p, c_void_p, P(s2s_attn_dims), c_void_p, c_int, c_int, c_int, c_void_p,
                                    c_size_t]),
     ("s2s_attn_beam_mlp_input", c_void_p, [P(s2s_attn_dims), c_int, c_int, c_void_p]),
@@ -175,6 +178,7 @@ S2S_CTX_OVERLAP = 2
 S2S_ZERO_GRADS = 1
 S2S_NORMALIZE_NLL = 2
 S2S_BUCKET_EVENTS = 4
+S2S_FORWARD_ONLY = 8
 S2S_ATTN_NPARAMS = 17
 S2S_ATTN_NPARAMS_HYBRID = 20
 S2S_ATTN_NPARAMS_LSTM = 36

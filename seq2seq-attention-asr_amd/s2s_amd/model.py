@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-from .nn import _bytes, dptr, get_context, lengths_tensor, saved_view, stream_ptr
+from .nn import _bytes, beam_search_call, dptr, get_context, lengths_tensor, saved_view, stream_ptr
 
 
 @dataclasses.dataclass
@@ -234,8 +234,21 @@ class ChorowskiBaseline:
         return self._step(x, labels, scale, zero_grads, normalizeNLL, logp, nll, stream, dropout_seed, dropout_mask,
                           bucket_events, frame_lengths, label_lengths)
 
+    def forward(self, x, labels, frame_lengths=None, label_lengths=None, normalizeNLL=False, stream=None):
+        """autoencoder:forward for validation (timit/timit.lua:368-417): encoder forward, decoder forward and the
+        per-utterance nll, with no backward -- self.grads is neither read nor written.  Returns (nll (B,),
+        logp (B, T, O)) in the same module-owned outputs as step(), bitwise equal to a step's on the same inputs;
+        encoder_output() and the decoder accessors are valid afterwards.  Lengths and stream as in step()."""
+        args = (x, labels, None, False, normalizeNLL, None, None, stream, None, None, False, frame_lengths,
+                label_lengths, True)
+        if stream is not None and stream != torch.cuda.current_stream(self.device):
+            stream.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(stream):
+                return self._step(*args)
+        return self._step(*args)
+
     def _step(self, x, labels, scale, zero_grads, normalizeNLL, logp, nll, stream, dropout_seed, dropout_mask,
-              bucket_events, frame_lengths, label_lengths):
+              bucket_events, frame_lengths, label_lengths, forward_only=False):
         # every torch op here runs on the step's stream (step() entered its context when it differs)
         if x.dim() == 2:
             x = x[None]
@@ -293,8 +306,11 @@ class ChorowskiBaseline:
         flags = (_lib.S2S_ZERO_GRADS if zero_grads else 0) | (_lib.S2S_NORMALIZE_NLL if normalizeNLL else 0)
         if bucket_events:
             flags |= _lib.S2S_BUCKET_EVENTS
+        if forward_only:
+            flags |= _lib.S2S_FORWARD_ONLY
         st = ctypes.c_void_p(stream.cuda_stream) if stream is not None else stream_ptr()
-        check(lib.s2s_model_step(self.ctx.handle, st, ctypes.byref(d), dptr(self.params), dptr(self.grads), dptr(x),
+        check(lib.s2s_model_step(self.ctx.handle, st, ctypes.byref(d), dptr(self.params),
+                                 None if forward_only else dptr(self.grads), dptr(x),
                                  dptr(lab), float(scale), flags, dptr(logp), dptr(nll), dptr(ws), ws.numel()))
         self._last = (B, L, T)
         return nll, logp
@@ -337,6 +353,95 @@ class ChorowskiBaseline:
             for j, i in enumerate(idx):
                 logps[i] = lp[j, :Ts[j]].clone()  # lp is the module-owned output, reused by the next batch
         return nll, logps
+
+    # ---- validation (timit/timit.lua:368-417)
+    def BeamSearch(self, eos, K=5, maxseqlength=None, frame_lengths=None, maxseqlengths=None):
+        """decoder:BeamSearch(encoder.output, eos, K, maxseqlen) (timit/timit.lua:397-401) on the annotations of
+        the last step / forward, with the model's decoder parameters, in evaluate() mode.  frame_lengths (B,):
+        the padded batch's frames per utterance; maxseqlengths (B,) defaults to them, maxseqlength to L.
+        Returns (tokens (B, maxseqlength + 1) padded with -1, lengths (B), scores (B))."""
+        h = self.encoder_output()
+        B, L, _ = h.shape
+        maxlen = int(maxseqlength or L)
+        c = self.cfg
+        md = _lib.s2s_model_dims(B, L, 1, c.inputFrameSize, c.hiddenFrameSize, c.outputFrameSize, c.numLayers,
+                                 c.scoreDepth, c.stateDepth, c.outputDepth, c.mlpDepth, c.maxoutWindow, c.penalty, 0.0)
+        d = _lib.s2s_attn_dims()
+        check(lib.s2s_model_attn_dims(ctypes.byref(md), ctypes.byref(d)))
+        ptrs = []
+        for i in range(_lib.S2S_ATTN_NPARAMS):
+            off = lib.s2s_model_param_offset(ctypes.byref(md), 6 * c.numLayers + i, None)
+            ptrs.append(self.params.data_ptr() + 4 * off)
+        run = beam_search_call(self.ctx.handle, d, h, _lib.ptr_array(ptrs), eos, K, maxlen, frame_lengths,
+                               maxseqlengths)
+        return run.out, run.olen, run.osc
+
+    def Evaluate(self, xs, ys, K=5, max_batch=32, eos=None, token_map=None):
+        """Evaluate(data) (timit/timit.lua:368-417) over utterances xs[i] (L_i, F) float32 CUDA tensors with labels
+        ys[i] (T_i,) 0-based, in evaluate() mode: sorted by length, cut into padded batches of at most max_batch,
+        each run through the forward-only pass with lengths, then the beam search on encoder_output() with
+        frame_lengths and maxseqlengths = L_b (:400), then the edit distance on the device.  eos = the last label
+        (:398), which must be the same for every utterance (ValueError otherwise).  token_map (O,): applied to
+        prediction and target before the distance (mapPhonemes, :403-406).  Returns (accuracy = sum numCorrect /
+        sum T_b (:391-394, :413), NLL = sum_b nll_b / N with nll_b = -sum labelmask . logp unnormalised (:389,
+        :414), PER = mean_b dist_b / T_b (:410, :415), predlist: the unmapped predictions, int64 CPU tensors), all
+        in input order.  self.eval_detail keeps the per-utterance nll, numCorrect, distances and beam scores."""
+        from .nn import edit_distance
+        N = len(xs)
+        if N == 0 or len(ys) != N:
+            raise ValueError("Evaluate needs one label sequence per utterance")
+        labs = [torch.as_tensor(y).to(torch.int64).reshape(-1).cpu() for y in ys]
+        if any(y.numel() == 0 for y in labs):
+            raise ValueError("Evaluate: empty label sequence")
+        lasts = {int(y[-1]) for y in labs}
+        if eos is not None:
+            lasts.add(int(eos))
+        if len(lasts) != 1:
+            raise ValueError(f"Evaluate: eos (the last label) differs between utterances: {sorted(lasts)}")
+        eos = lasts.pop()
+        tmap = None
+        if token_map is not None:
+            tmap = torch.as_tensor(token_map).to(torch.int32).reshape(-1).to(self.device)
+            if tmap.numel() != self.cfg.outputDepth:
+                raise ValueError("token_map must have outputDepth entries")
+        nll = [0.0] * N
+        correct, dist, score, preds = [0] * N, [0] * N, [0.0] * N, [None] * N
+        order = sorted(range(N), key=lambda i: (xs[i].shape[0], labs[i].numel()))
+        was_train = self.train
+        self.evaluate()
+        try:
+            for c0 in range(0, N, int(max_batch)):
+                idx = order[c0:c0 + int(max_batch)]
+                Ls = [xs[i].shape[0] for i in idx]
+                Ts = [labs[i].numel() for i in idx]
+                L, T, F = max(Ls), max(Ts), xs[idx[0]].shape[1]
+                x = torch.zeros((len(idx), L, F), device=self.device, dtype=torch.float32)
+                y = torch.zeros((len(idx), T), dtype=torch.int32)
+                for j, i in enumerate(idx):
+                    x[j, :Ls[j]] = xs[i]
+                    y[j, :Ts[j]] = labs[i].to(torch.int32)
+                y = y.to(self.device)
+                tl = torch.tensor(Ts, dtype=torch.int32, device=self.device)
+                n, logp = self.forward(x, y, frame_lengths=Ls, label_lengths=Ts, normalizeNLL=False)
+                live = torch.arange(T, device=self.device)[None, :] < tl[:, None]
+                ok = ((logp.argmax(-1).to(torch.int32) == y) & live).sum(1)
+                out, olen, osc = self.BeamSearch(eos, K, frame_lengths=Ls)
+                pm, tm = out, y
+                if tmap is not None:
+                    pm = torch.where(out >= 0, tmap[out.clamp(min=0).long()], out)
+                    tm = tmap[y.long()]
+                dd = edit_distance(pm, olen, tm, tl)
+                n_c, ok_c, dd_c, out_c, olen_c, osc_c = (t.cpu() for t in (n, ok, dd, out, olen, osc))
+                for j, i in enumerate(idx):
+                    nll[i], correct[i], dist[i], score[i] = float(n_c[j]), int(ok_c[j]), int(dd_c[j]), float(osc_c[j])
+                    preds[i] = out_c[j, :int(olen_c[j])].to(torch.int64).clone()
+        finally:
+            self.train = was_train
+        Tn = [y.numel() for y in labs]
+        self.eval_detail = {"nll": nll, "numCorrect": correct, "dist": dist, "score": score, "T": Tn}
+        accuracy = sum(correct) / sum(Tn)
+        per = [dist[i] / Tn[i] for i in range(N)]
+        return accuracy, sum(nll) / N, sum(per) / N, preds
 
     # ---- the decoder's trainer-visible surface after a step (timit/timit.lua:519-521, 534-536)
     def _attn(self):

@@ -698,14 +698,19 @@ class Attention(Module):
     def accGradParameters(self, input, gradOutput, scale=1.0):
         pass
 
-    def BeamSearch(self, annotations, eos, K=5, maxseqlength=None, finished=False):
+    def BeamSearch(self, annotations, eos, K=5, maxseqlength=None, finished=False, frame_lengths=None,
+                   maxseqlengths=None):
         """decoder:BeamSearch(annotations, eos, K, maxseqlength) (Attention.lua:332-438) in evaluate()
         mode.  annotations (L, A) -> 1-D int tensor (the prediction, 0-based tokens, eos last when it
         finished on eos); (B, L, A) -> (tokens (B, maxseqlength + 1) padded with -1, lengths (B),
         scores (B)).  maxseqlength defaults to L (:337).  Content or hybrid attention, GRU or LSTM
         decoder_recurrent; an external decoder_mlp runs between the search's step and advance calls on
-        the (B*K, S+A) hypothesis rows.  finished=True (a diagnostic) also returns every finished hypothesis,
-        the reference's y_finished / p_finished (:375-376), in finishing order: (nfin (B), flen (B, K),
+        the (B*K, S+A) hypothesis rows.
+        frame_lengths (B,): a padded batch -- frames >= L_b of utterance b take no part (content attention only;
+        the module's training attribute frame_lengths is never used here).  maxseqlengths (B,): each utterance's
+        own length limit, in [1, maxseqlength]; defaults to frame_lengths when those are given (timit.lua:400
+        searches each utterance to its own frame count).  finished=True (a diagnostic) also returns every finished
+        hypothesis, the reference's y_finished / p_finished (:375-376), in finishing order: (nfin (B), flen (B, K),
         fscore (B, K), fseq (B, K, maxseqlength + 1)); entries at or beyond nfin[b] are unspecified."""
         h = annotations
         if h.dim() not in (2, 3):
@@ -718,21 +723,20 @@ class Attention(Module):
         B, L = h.shape[0], h.shape[1]
         maxlen = int(maxseqlength or L)
         was_train, self.train = self.train, False
-        d = self._dims(h, 1)
-        self.train = was_train
-        d.frame_lengths = d.label_lengths = None  # the utterances' whole annotation sequences are searched
+        was_len, self.frame_lengths, self.label_lengths = (self.frame_lengths, self.label_lengths), None, None
+        try:
+            d = self._dims(h, 1)
+        finally:
+            self.train = was_train
+            self.frame_lengths, self.label_lengths = was_len
         dev = h.device
         self._sync_pad()
-        ws = _bytes(lib.s2s_attn_beam_workspace_bytes(ctypes.byref(d), K, maxlen), dev)
-        out = torch.empty((B, maxlen + 1), dtype=torch.int32, device=dev)
-        olen = torch.empty(B, dtype=torch.int32, device=dev)
-        osc = torch.empty(B, dtype=torch.float32, device=dev)
         params = self._ptrs(False)
         ctx, st = get_context(dev.index).handle, stream_ptr()
-        if not self.external_mlp:
-            check(lib.s2s_attn_beam_search(ctx, st, ctypes.byref(d), dptr(h), params, int(eos), int(K), maxlen,
-                                           dptr(out), maxlen + 1, dptr(olen), dptr(osc), dptr(ws), ws.numel()))
-        else:
+        run = beam_search_call(ctx, d, h, params, eos, K, maxlen, frame_lengths, maxseqlengths,
+                               launch=not self.external_mlp)
+        ws, out, olen, osc, mls = run.ws, run.out, run.olen, run.osc, run.mls
+        if self.external_mlp:
             R, W = B * int(K), self.stateDepth + self.annotationDepth
             p = lib.s2s_attn_beam_mlp_input(ctypes.byref(d), int(K), maxlen, dptr(ws))
             off = p - ws.data_ptr()
@@ -744,6 +748,9 @@ class Attention(Module):
             try:
                 check(lib.s2s_attn_beam_init(ctx, st, ctypes.byref(d), dptr(h), params, int(eos), int(K), maxlen,
                                              dptr(ws), ws.numel()))
+                if mls is not None:
+                    check(lib.s2s_attn_beam_set_maxlens(ctx, st, ctypes.byref(d), int(K), maxlen, dptr(mls),
+                                                        dptr(ws)))
                 for count in range(maxlen + 1):
                     check(lib.s2s_attn_beam_step(ctx, st, ctypes.byref(d), params, int(K), maxlen, count, dptr(ws),
                                                  ws.numel()))
@@ -819,6 +826,42 @@ class Attention(Module):
         d = self._d
         vh = saved_view(self._saved, lib.s2s_attn_vh(ctypes.byref(d), dptr(self._saved)), (d.B, d.L, d.scoreDepth))
         return vh[..., :self.scoreDepth]
+
+
+class BeamRun:
+    """Buffers of one beam search (beam_search_call); the lengths tensors stay alive with it."""
+
+
+def beam_search_call(ctx, d, h, params, eos, K, maxlen, frame_lengths=None, maxseqlengths=None, launch=True):
+    """The one place a search's arguments are prepared (Attention.BeamSearch, ChorowskiBaseline.BeamSearch): d is
+    the decoder's s2s_attn_dims for h (B, L, A) with no lengths set; frame_lengths (B,) in [1, L] go into it
+    (refused with hybrid attention), maxseqlengths (B,) in [1, maxlen] default to them; workspace and outputs are
+    allocated; with launch the whole search runs (s2s_attn_beam_search / _ragged), otherwise the caller steps it."""
+    B, L, dev = h.shape[0], h.shape[1], h.device
+    run = BeamRun()
+    run.fl = run.mls = None
+    if frame_lengths is not None:
+        if d.hybridAttendFeatureMaps > 0:
+            raise S2SArgumentError("BeamSearch: frame_lengths with hybrid attention is unsupported "
+                                   "(search such an utterance's own frames)")
+        run.fl = lengths_tensor(frame_lengths, B, L, dev)
+        d.frame_lengths = run.fl.data_ptr()
+        if maxseqlengths is None:
+            maxseqlengths = torch.as_tensor(frame_lengths).to(torch.int64).reshape(-1).clamp(max=maxlen)
+    if maxseqlengths is not None:
+        run.mls = lengths_tensor(maxseqlengths, B, maxlen, dev)
+    run.ws = _bytes(lib.s2s_attn_beam_workspace_bytes(ctypes.byref(d), int(K), maxlen), dev)
+    run.out = torch.empty((B, maxlen + 1), dtype=torch.int32, device=dev)
+    run.olen = torch.empty(B, dtype=torch.int32, device=dev)
+    run.osc = torch.empty(B, dtype=torch.float32, device=dev)
+    if launch:
+        head = (ctx, stream_ptr(), ctypes.byref(d), dptr(h), params, int(eos), int(K), maxlen)
+        tail = (dptr(run.out), maxlen + 1, dptr(run.olen), dptr(run.osc), dptr(run.ws), run.ws.numel())
+        if run.mls is not None:
+            check(lib.s2s_attn_beam_search_ragged(*head, dptr(run.mls), *tail))
+        else:
+            check(lib.s2s_attn_beam_search(*head, *tail))
+    return run
 
 
 def saved_view(buf, p, shape, dtype=torch.float32):
