@@ -41,27 +41,37 @@ struct s2s_debug_gemm_plan {
   int launched, bm, bn, kslice, nblocks, reduced;
   int splits[s2s::kMaxGemmBatch];  // per problem, in the caller's order; 0 = skipped
 };
-extern "C" int s2s_debug_gemm_batch(s2s_stream_t stream, const s2s_debug_gemm_problem* probs, int nprob, int transA,
-                                    int transB, float* ws, size_t ws_floats, s2s_debug_gemm_plan* plan) {
+static s2s::GemmProblem to_problem(const s2s_debug_gemm_problem& q) {
+  s2s::GemmProblem p{q.A, q.B, q.C, q.bias, q.lda, q.ldb, q.ldc, q.M, q.N, q.K, q.alpha, q.beta};
+  p.Mread = q.Mread;
+  p.Nread = q.Nread;
+  p.rbias = q.rbias;
+  p.relu = q.relu;
+  return p;
+}
+// the same with the operand precision (tests/test_gpu_gemm_bf16.py): bf16 = 1 runs gemm_f32's bf16 tile family
+// (gemm_bf16_kernel) on every problem -- it clears the calling thread's staging buffer (every C-ABI entry with a
+// context sets it again), so none goes to the big-tile GEMM
+extern "C" int s2s_debug_gemm_batch_prec(s2s_stream_t stream, const s2s_debug_gemm_problem* probs, int nprob, int transA,
+                                         int transB, int bf16, float* ws, size_t ws_floats, s2s_debug_gemm_plan* plan) {
   S2S_REQUIRE(probs != nullptr && plan != nullptr, "debug_gemm_batch: null argument");
   S2S_REQUIRE(nprob >= 1 && nprob <= s2s::kMaxGemmBatch,
               "debug_gemm_batch: 1 .. " + std::to_string(s2s::kMaxGemmBatch) + " problems");
   s2s::GemmProblem p[s2s::kMaxGemmBatch];
-  for (int i = 0; i < nprob; ++i) {
-    const s2s_debug_gemm_problem& q = probs[i];
-    p[i] = s2s::GemmProblem{q.A, q.B, q.C, q.bias, q.lda, q.ldb, q.ldc, q.M, q.N, q.K, q.alpha, q.beta};
-    p[i].Mread = q.Mread;
-    p[i].Nread = q.Nread;
-    p[i].rbias = q.rbias;
-    p[i].relu = q.relu;
-  }
-  s2s::set_gemm_precision(s2s::kGemmF32);
+  for (int i = 0; i < nprob; ++i) p[i] = to_problem(probs[i]);
+  if (bf16) s2s::set_gemm_stage(nullptr);
+  s2s::set_gemm_precision(bf16 ? s2s::kGemmBf16 : s2s::kGemmF32);
   const int rc = s2s::gemm_f32(static_cast<hipStream_t>(stream), p, nprob, transA != 0, transB != 0,
                                s2s::GemmWs{ws, ws ? ws_floats : 0});
+  s2s::set_gemm_precision(s2s::kGemmF32);
   const s2s::GemmLastPlan& lp = s2s::gemm_last_plan();
   *plan = s2s_debug_gemm_plan{lp.launched, lp.bm, lp.bn, lp.kslice, lp.nblocks, lp.reduced, {}};
   for (int i = 0; i < s2s::kMaxGemmBatch; ++i) plan->splits[i] = lp.splits[i];
   return rc;
+}
+extern "C" int s2s_debug_gemm_batch(s2s_stream_t stream, const s2s_debug_gemm_problem* probs, int nprob, int transA,
+                                    int transB, float* ws, size_t ws_floats, s2s_debug_gemm_plan* plan) {
+  return s2s_debug_gemm_batch_prec(stream, probs, nprob, transA, transB, 0, ws, ws_floats, plan);
 }
 // one thin entry per helper of gemm_f32.hip
 extern "C" int s2s_debug_colsum(s2s_stream_t stream, const float* X, long ldx, int M, int N, float alpha, float beta,
@@ -117,6 +127,16 @@ extern "C" int s2s_debug_gemm_big_run(s2s_ctx* ctx, s2s_stream_t stream, int tra
   q.relu = relu;
   bool d = false;
   const int rc = s2s::gemm_big_bf16(static_cast<hipStream_t>(stream), q, transA != 0, transB != 0, &d);
+  *done = d ? 1 : 0;
+  return rc;
+}
+// the same from a whole problem description (rbias, Mread, Nread: what the big-tile GEMM must decline)
+extern "C" int s2s_debug_gemm_big_problem(s2s_ctx* ctx, s2s_stream_t stream, const s2s_debug_gemm_problem* prob,
+                                          int transA, int transB, int* done) {
+  S2S_TRY(set_device(ctx));
+  S2S_REQUIRE(prob != nullptr && done != nullptr, "null argument");
+  bool d = false;
+  const int rc = s2s::gemm_big_bf16(static_cast<hipStream_t>(stream), to_problem(*prob), transA != 0, transB != 0, &d);
   *done = d ? 1 : 0;
   return rc;
 }

@@ -255,7 +255,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt(BigGemm g) {
     for (int q = 0; q < FN; ++q) {
       const int col = n0 + wn * TN + 16 * q + lr;
       if (col >= g.N) continue;
-      const float bv = (!g.part && g.bias) ? g.bias[col] : 0.f;
+      const bool has_bias = !g.part && g.bias;  // (no bias: nothing is added, so -0 stays -0 as in the reduce)
+      const float bv = has_bias ? g.bias[col] : 0.f;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = m0 + wm * TM + 16 * f + 4 * lq + r;
@@ -263,7 +264,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bf16_nt(BigGemm g) {
         if (g.part) {
           g.part[((long)s * g.M + row) * g.N + col] = acc[f][q][r];
         } else {
-          float v = g.alpha * acc[f][q][r] + bv;
+          float v = g.alpha * acc[f][q][r];
+          if (has_bias) v += bv;
           float* c = g.C + (long)row * g.ldc + col;
           if (g.beta != 0.f) v += g.beta * *c;
           if (g.relu) v = fmaxf(v, 0.f);
@@ -317,8 +319,23 @@ int launch_nt(hipStream_t st, const BigGemm& g) {
 
 bool gemm_big_enabled() { return g_gemm_big != 0; }
 
+static thread_local GemmBigLastPlan t_big_last;
+const GemmBigLastPlan& gemm_big_last_plan() { return t_big_last; }
+static thread_local int t_force_bm = 0, t_force_bn = 0, t_force_s = 0;  // gemm_big_force
+bool gemm_big_force(int bm, int bn, int splits) {
+  const bool tile = (bm == 0 && bn == 0) || (bm == 256 && bn == 256) || (bm == 256 && bn == 128) || (bm == 128 && bn == 128);
+  if (!tile || splits < 0 || splits > 256) return false;
+  t_force_bm = bm;
+  t_force_bn = bn;
+  t_force_s = splits;
+  return true;
+}
+
 int gemm_big_bf16(hipStream_t st, const GemmProblem& q, bool transA, bool transB, bool* done) {
   *done = false;
+  GemmBigLastPlan& rec = t_big_last;
+  rec = GemmBigLastPlan{};
+  rec.declined = 1;
   if (!g_gemm_big || !t_stage || q.M <= 0 || q.N <= 0 || q.K <= 0 || q.rbias || q.Mread || q.Nread) return 0;
   const int M = q.M, N = q.N, K = q.K, Kp = (K + kBK - 1) / kBK * kBK, nkt = Kp / kBK;
   // Tile and split-K from a time model: per-CU rates of the three tiles (measured on MI355X, tools/gemm_big_bench.py:
@@ -341,9 +358,14 @@ int gemm_big_bf16(hipStream_t st, const GemmProblem& q, bool transA, bool transB
       if (t < best * 0.98) { best = t; BM = c.bm; BN = c.bn; S = s; }
     }
   }
+  if (t_force_bm) { BM = t_force_bm; BN = t_force_bn; }  // test override: the same kernels, chosen by hand
+  if (t_force_s) S = t_force_s;
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN, tiles = tiles_m * tiles_n;
   const int kslice = (nkt + S - 1) / S;
   S = (nkt + kslice - 1) / kslice;
+  // (the override never runs another count than the one asked for: nothing is launched)
+  S2S_REQUIRE(!t_force_s || S == t_force_s, "gemm_big_bf16: the forced split count does not divide this problem's " +
+                                                std::to_string(nkt) + " K-tiles into that many slices");
   const size_t abytes = (size_t)M * Kp * 2, bbytes = (size_t)N * Kp * 2;
   const size_t slab = S > 1 ? sizeof(float) * (size_t)S * M * N : 0;
   const size_t off_b = (abytes + 255) / 256 * 256, off_p = off_b + (bbytes + 255) / 256 * 256;
@@ -353,20 +375,22 @@ int gemm_big_bf16(hipStream_t st, const GemmProblem& q, bool transA, bool transB
   __bf16* Bh = reinterpret_cast<__bf16*>(stg + off_b);
   // operands -> [M][Kp] / [N][Kp] (A: element (m, k) at A[m lda + k], or A[k lda + m] when transA; B: (n, k) at
   // B[n ldb + k] when transB (the NT form), else B[k ldb + n])
-  auto stage_op = [&](const float* src, long ld, int R, bool rowc, __bf16* dst) -> int {
+  auto stage_op = [&](const float* src, long ld, int R, bool rowc, __bf16* dst, int* how) -> int {
     if (rowc) {
       hipLaunchKernelGGL(stage_rc_bf16, dim3((R + 63) / 64, Kp / 64), dim3(256), 0, st, src, ld, R, K, Kp, dst);
+      *how = kStageRc;
     } else {
       const long n8 = (long)R * Kp / 8;
       const int vec = (ld % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) ? 1 : 0;
       const unsigned blocks = (unsigned)std::min<long>(4096, (n8 + 255) / 256);
       hipLaunchKernelGGL(stage_kc_bf16, dim3(blocks), dim3(256), 0, st, src, ld, R, K, Kp, n8, vec, dst);
+      *how = vec ? kStageKcVec : kStageKcScalar;
     }
     S2S_CHECK_HIP(hipGetLastError());
     return 0;
   };
-  S2S_TRY(stage_op(q.A, q.lda, M, transA, Ah));
-  S2S_TRY(stage_op(q.B, q.ldb, N, !transB, Bh));
+  S2S_TRY(stage_op(q.A, q.lda, M, transA, Ah, &rec.stage_a));
+  S2S_TRY(stage_op(q.B, q.ldb, N, !transB, Bh, &rec.stage_b));
   BigGemm g{};
   g.A = Ah;
   g.B = Bh;
@@ -397,6 +421,14 @@ int gemm_big_bf16(hipStream_t st, const GemmProblem& q, bool transA, bool transB
     hipLaunchKernelGGL(bf16_splitk_reduce, dim3((unsigned)std::min<long>(2048, (mn + 255) / 256)), dim3(256), 0, st, g);
     S2S_CHECK_HIP(hipGetLastError());
   }
+  rec.launched = 1;
+  rec.declined = 0;
+  rec.bm = BM;
+  rec.bn = BN;
+  rec.S = S;
+  rec.kslice = kslice;
+  rec.nblocks = g.nblocks;
+  rec.forced = (t_force_bm || t_force_s) ? 1 : 0;
   *done = true;
   ++g_big_calls;
   return 0;
@@ -405,4 +437,16 @@ int gemm_big_bf16(hipStream_t st, const GemmProblem& q, bool transA, bool transB
 }  // namespace s2s
 
 extern "C" void s2s_debug_gemm_big(int on) { s2s::g_gemm_big = on; }
+// test override of the big GEMM's tile and split count on the calling thread (gemm_big_force; 0, 0, 0 = the time
+// model); 0 when accepted, 1 when refused (nothing changes)
+extern "C" int s2s_debug_gemm_big_force(int bm, int bn, int splits) { return s2s::gemm_big_force(bm, bn, splits) ? 0 : 1; }
+// the record of the calling thread's last gemm_big_bf16 call (GemmBigLastPlan, field by field)
+struct s2s_debug_gemm_big_plan {
+  int launched, declined, bm, bn, S, kslice, nblocks, stage_a, stage_b, forced;
+};
+extern "C" void s2s_debug_gemm_big_last(s2s_debug_gemm_big_plan* out) {
+  const s2s::GemmBigLastPlan& p = s2s::gemm_big_last_plan();
+  if (out) *out = s2s_debug_gemm_big_plan{p.launched, p.declined, p.bm, p.bn, p.S, p.kslice, p.nblocks, p.stage_a,
+                                           p.stage_b, p.forced};
+}
 extern "C" long s2s_debug_gemm_big_calls() { return s2s::g_big_calls; }

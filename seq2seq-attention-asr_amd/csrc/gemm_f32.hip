@@ -789,10 +789,9 @@ static GemmPlan plan_gemm(const GemmProblem* p, int n, size_t ws_floats, bool bf
 
 template <bool TA, bool TB>
 static void launch_tiles(hipStream_t st, const GemmPlan& pl, dim3 grid, const GemmLaunch& L, bool bf16) {
-  if (bf16) {
+  if (bf16) {  // plan_gemm's bf16 branch gives 64 x 64, 64 x 128 or 128 x 128 (its wider tile always has bn = 128)
     if (pl.bm == 128 && pl.bn == 128) hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, 128, 128>), grid, dim3(256), 0, st, L);
     else if (pl.bn == 128) hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, 64, 128>), grid, dim3(256), 0, st, L);
-    else if (pl.bm == 128) hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, 128, 64>), grid, dim3(256), 0, st, L);
     else hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, 64, 64>), grid, dim3(256), 0, st, L);
     return;
   }

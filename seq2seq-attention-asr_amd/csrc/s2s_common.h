@@ -206,6 +206,21 @@ void* stage_acquire(hipStream_t st, size_t bytes);  // that buffer with >= bytes
 // when it does not apply (rbias / Mread / Nread, no staging buffer, disabled by s2s_debug_gemm_big(0)).
 bool gemm_big_enabled();
 int gemm_big_bf16(hipStream_t st, const GemmProblem& q, bool transA, bool transB, bool* done);
+// What the calling thread's last gemm_big_bf16 call did, written by that call from the values it launched with
+// (tests/test_gpu_gemm_bf16.py asserts it: s2s_debug_gemm_big_last).  declined = 1: nothing was launched.  stage_a /
+// stage_b: how each operand was staged -- kStageRc (row-contiguous, through the LDS transpose), kStageKcScalar or
+// kStageKcVec (K-contiguous: guarded scalar loads, or float4 loads of a 16-byte-aligned operand with ld % 4 == 0).
+// kslice counts K-tiles of 64; forced = 1 when the test override chose the tile or the split (gemm_big_force).
+enum { kStageRc = 0, kStageKcScalar = 1, kStageKcVec = 2 };
+struct GemmBigLastPlan {
+  int launched = 0, declined = 0, bm = 0, bn = 0, S = 0, kslice = 0, nblocks = 0, stage_a = -1, stage_b = -1, forced = 0;
+};
+const GemmBigLastPlan& gemm_big_last_plan();
+// Test override of the time model (thread-local): tile bm x bn (0 x 0: the model's) and split count (0: the
+// model's).  Only the three tiles the kernel is built for and 0 .. 256 slices are accepted (false otherwise, nothing
+// changes); a call whose K-tiles cannot be cut into exactly the forced count of slices (slices are whole K-tiles of
+// equal length but the last: count == ceil(nkt / ceil(nkt / count))) fails instead of running another split.
+bool gemm_big_force(int bm, int bn, int splits);
 // Implicit-GEMM SpatialConvolutionMM on bf16 MFMA (conv_bf16.inc): no im2col panel.  Forward y (B, Cout, Ho,
 // Wo) = conv(x) + bias (per channel), ReLU when relu; input gradient dx (B, Cin, H, W) (+)= transposed
 // convolution of dyt (Cout, B Ho Wo) -- the ReLU-masked output gradient -- with W.  scratch:

@@ -9,95 +9,22 @@ and slice length the library reports for the launch it made (GemmLastPlan), so a
 into unsplit tests unnoticed.  Only the precision leg (random normal data) has a tolerance: the project's own
 max|gpu - ref| <= 2e-5 max|ref|; it prints the measured ratio of every case.
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 import gemm_case as gc
+from gemm_gpu import WS_FLOATS, load, run_batch, run_exact  # the runner the bf16 tests share
+from gemm_gpu import dev as _dev, ok as _ok, ptr as _ptr, same_bits as _same_bits, stream as _stream
 
 pytestmark = pytest.mark.gpu
-
-WS_FLOATS = 8 << 20  # kGemmWsFloats
 
 
 @pytest.fixture(scope="module")
 def s2s():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    from s2s_amd import _lib
-    e = gc.declare(_lib.lib)
-    e.lib = _lib.lib
-    e.ws = torch.empty(WS_FLOATS, device="cuda")
-    assert e.ws.data_ptr() % 16 == 0
-    return e
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _dev(buf):
-    t = torch.from_numpy(np.array(buf, dtype=np.float32, copy=True)).cuda()
-    assert t.data_ptr() % 16 == 0
-    return t
-
-
-def _ptr(t, off=0):
-    return t.data_ptr() + 4 * off
-
-
-def _ok(s2s, rc):
-    assert rc == 0, s2s.lib.s2s_last_error().decode()
-
-
-def _same_bits(got, expect, win=None, what=""):
-    g, e = gc.bits(got), gc.bits(expect)
-    if np.array_equal(g, e):
-        return
-    bad = np.flatnonzero(g != e)
-    where = ""
-    if win is not None:
-        inside = ~win.outside()
-        where = f"; {int(inside[bad].sum())} inside the window, {int((~inside[bad]).sum())} outside (canary)"
-    i = int(bad[0])
-    raise AssertionError(f"{what}: {bad.size} of {g.size} words differ{where}; first at {i}: got {got[i]!r} "
-                         f"({g[i]:#010x}), expected {expect[i]!r} ({e[i]:#010x})")
-
-
-def run_batch(s2s, cases, ws_floats=WS_FLOATS, with_ws=True):
-    """All cases in one s2s_debug_gemm_batch call -> (the C arrays afterwards, the reported plan)."""
-    probs = (s2s.Problem * len(cases))()
-    cs, keep = [], []
-    for p, c in zip(probs, cases):
-        a, b, cd = _dev(c.A.buf), _dev(c.B.buf), _dev(c.C.buf)
-        p.A, p.B, p.C = _ptr(a, c.A.off), _ptr(b, c.B.off), _ptr(cd, c.C.off)
-        p.lda, p.ldb, p.ldc = c.A.ld, c.B.ld, c.C.ld
-        if c.bias is not None:
-            bd = _dev(c.bias.buf)
-            p.bias = _ptr(bd, c.bias.off)
-            keep.append(bd)
-        if c.rbias is not None:
-            rd = _dev(c.rbias.buf)
-            p.rbias = _ptr(rd, c.rbias.off)
-            keep.append(rd)
-        p.M, p.N, p.K, p.alpha, p.beta = c.M, c.N, c.K, c.alpha, c.beta
-        p.Mread, p.Nread, p.relu = c.Mread, c.Nread, c.relu
-        keep += [a, b]
-        cs.append(cd)
-    plan = s2s.Plan()
-    rc = s2s.lib.s2s_debug_gemm_batch(_stream(), probs, len(cases), cases[0].tA, cases[0].tB,
-                                      s2s.ws.data_ptr() if with_ws else None, ws_floats, ctypes.byref(plan))
-    _ok(s2s, rc)
-    torch.cuda.synchronize()
-    return [t.cpu().numpy() for t in cs], plan
-
-
-def run_exact(s2s, c, **kw):
-    (out,), plan = run_batch(s2s, [c], **kw)
-    _same_bits(out, c.expect, c.C, f"{(c.tA, c.tB, c.M, c.N, c.K)} alpha {c.alpha} beta {c.beta}")
-    return out, plan
+    return load()
 
 
 def _tiles(c):
