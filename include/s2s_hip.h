@@ -307,6 +307,15 @@ int s2s_smaxpool_bwd(s2s_ctx* ctx, s2s_stream_t stream, int B, int C, int H, int
 int s2s_swap12(s2s_ctx* ctx, s2s_stream_t stream, int B, int D1, int D2, int D3, const float* x, float* y);
 int s2s_relu_fwd(s2s_ctx* ctx, s2s_stream_t stream, long n, const float* x, float* y);
 int s2s_relu_bwd(s2s_ctx* ctx, s2s_stream_t stream, long n, const float* x, const float* dy, float* dx);
+/* Batch assembly of variable-length utterances on the device (one launch each, capturable).  Utterance b is
+ * (C, L_b, F), contiguous, at src + offsets[b] (element offsets), L_b = lengths[b]; offsets and lengths are device
+ * arrays.  dst (B, C, Lmax, F): dst[b, c, l, :] = utterance b's frame l for l < min(L_b, Lmax), 0 past it
+ * (lengths above Lmax are clamped: the first Lmax frames are copied).  Labels likewise: dst (B, Tmax),
+ * dst[b, t] = src[offsets[b] + t] for t < min(lengths[b], Tmax), 0 past it. */
+int s2s_pad_batch(s2s_ctx* ctx, s2s_stream_t stream, int B, int C, int Lmax, int F, const float* src,
+                  const long* offsets, const int* lengths, float* dst);
+int s2s_pad_labels(s2s_ctx* ctx, s2s_stream_t stream, int B, int Tmax, const int* src, const long* offsets,
+                   const int* lengths, int* dst);
 /* nn.LogSoftMax over `rows` rows of n (the output layer of an external decoder_mlp): forward and
  * dx = dy - exp(y) * sum(dy). */
 int s2s_logsoftmax_fwd(s2s_ctx* ctx, s2s_stream_t stream, long rows, int n, const float* x, float* y);

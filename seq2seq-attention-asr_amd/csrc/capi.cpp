@@ -548,6 +548,18 @@ int s2s_swap12(s2s_ctx* ctx, s2s_stream_t stream, int B, int D1, int D2, int D3,
   S2S_REQUIRE(x && y && x != y, "Transpose2: null or in-place argument");
   return swap12(static_cast<hipStream_t>(stream), B, D1, D2, D3, x, y);
 }
+int s2s_pad_batch(s2s_ctx* ctx, s2s_stream_t stream, int B, int C, int Lmax, int F, const float* src,
+                  const long* offsets, const int* lengths, float* dst) {
+  S2S_TRY(set_device(ctx));
+  S2S_REQUIRE(src && offsets && lengths && dst, "pad_batch: null argument");
+  return pad_batch(static_cast<hipStream_t>(stream), B, C, Lmax, F, src, offsets, lengths, dst);
+}
+int s2s_pad_labels(s2s_ctx* ctx, s2s_stream_t stream, int B, int Tmax, const int* src, const long* offsets,
+                   const int* lengths, int* dst) {
+  S2S_TRY(set_device(ctx));
+  S2S_REQUIRE(src && offsets && lengths && dst, "pad_labels: null argument");
+  return pad_labels(static_cast<hipStream_t>(stream), B, Tmax, src, offsets, lengths, dst);
+}
 int s2s_relu_fwd(s2s_ctx* ctx, s2s_stream_t stream, long n, const float* x, float* y) {
   S2S_TRY(set_device(ctx));
   return relu_fwd(static_cast<hipStream_t>(stream), n, x, y);

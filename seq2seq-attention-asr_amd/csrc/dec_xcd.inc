@@ -1216,18 +1216,20 @@ __global__ __launch_bounds__(256) void dec_xcd_dvh(AttnK k, XArgs x) {
     k.DWEACC[((long)b * k.NCH + 2 * blk + fg) * SC + j] = dw[2 * fg][jl] + dw[2 * fg + 1][jl];
 }
 
-// VBAR[b][j] = mean over frames of Vh[b, :, j]  (reference point of the dws sums).
+// VBAR[b][j] = mean over the utterance's own frames of Vh[b, :, j]  (reference point of the dws sums; any point is
+// exact, but one that took in the padding frames of a variable-length batch would let their contents into the
+// sums' rounding).
 // grid (Sc/64, B): 64 columns per workgroup, the frames split over the 4 waves
 __device__ __forceinline__ void vbar_body(const AttnK& k, const XArgs& x, int cg, int b) {
   __shared__ float part[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = cg * 64 + lane;
-  const int L = k.L, SC = k.Sc;
+  const int L = frames_of(k, b), SC = k.Sc;  // (k.L without frame lengths: the same sums as ever)
   float s = 0.f;
   if (j < SC) {
     // eight frames' loads in flight per pass (the sum keeps its frame order): a 64-block launch, so each thread's
     // chain of L / 4 loads is the launch's length (the merged head launch 20.4 -> 17.9 us at config 2; sixteen
     // in flight: 18.8)
-    const float* v = k.Vh + ((long)b * L) * SC + j;
+    const float* v = k.Vh + ((long)b * k.L) * SC + j;
     int l = wave;
     for (; l + 28 < L; l += 32) {
       float q[8];

@@ -23,6 +23,9 @@ int smaxpool_fwd(hipStream_t st, int B, int C, int H, int W, int kW, int kH, int
 int smaxpool_bwd(hipStream_t st, int B, int C, int H, int W, int kW, int kH, int dW, int dH, const int* idx,
                  const float* dy, float* dx);
 int swap12(hipStream_t st, int B, int D1, int D2, int D3, const float* x, float* y);
+int pad_batch(hipStream_t st, int B, int C, int Lmax, int F, const float* src, const long* offsets,
+              const int* lengths, float* dst);
+int pad_labels(hipStream_t st, int B, int Tmax, const int* src, const long* offsets, const int* lengths, int* dst);
 int relu_fwd(hipStream_t st, long n, const float* x, float* y);
 int relu_bwd(hipStream_t st, long n, const float* x, const float* dy, float* dx);
 int logsoftmax_fwd(hipStream_t st, long rows, int n, const float* x, float* y);

@@ -260,6 +260,53 @@ __global__ void swap12_kernel(const float* __restrict__ x, int B, int D1, int D2
   }
 }
 
+// Batch assembly: utterance b = (C, L_b, F) contiguous at src + offsets[b] -> dst[b] = (C, Lmax, F), frames
+// l >= L_b zero.  blockIdx.y = b; L_b = lengths[b] is the source's frame stride, min(L_b, Lmax) frames are copied.
+// float4 path when F % 4 == 0 and both the utterance and its dst block are 16-byte aligned (a group of four
+// floats then never straddles a frame row); decided per utterance, uniform within the block.
+__global__ __launch_bounds__(256) void pad_batch_kernel(const float* __restrict__ src, const long* __restrict__ offsets,
+                                                        const int* __restrict__ lengths, int C, int Lmax, int F,
+                                                        float* __restrict__ dst) {
+  const int b = blockIdx.y;
+  const int Ls = max(lengths[b], 0);
+  const int Lc = min(Ls, Lmax);
+  const float* s = src + offsets[b];
+  const long n = (long)C * Lmax * F;
+  float* d = dst + (long)b * n;
+  const bool vec = (F & 3) == 0 && (((size_t)s | (size_t)d) & 15) == 0;
+  if (vec) {
+    const int F4 = F >> 2;
+    const long n4 = n >> 2;
+    const floatx4* s4 = reinterpret_cast<const floatx4*>(s);
+    floatx4* d4 = reinterpret_cast<floatx4*>(d);
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < n4; e += (long)gridDim.x * 256) {
+      const int f = (int)(e % F4);
+      const long cl = e / F4;
+      const int l = (int)(cl % Lmax), c = (int)(cl / Lmax);
+      floatx4 v = {0.f, 0.f, 0.f, 0.f};
+      if (l < Lc) v = s4[((long)c * Ls + l) * F4 + f];
+      d4[e] = v;
+    }
+  } else {
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
+      const int f = (int)(e % F);
+      const long cl = e / F;
+      const int l = (int)(cl % Lmax), c = (int)(cl / Lmax);
+      d[e] = l < Lc ? s[((long)c * Ls + l) * F + f] : 0.f;
+    }
+  }
+}
+
+// dst[b, t] = src[offsets[b] + t] for t < min(lengths[b], Tmax), else 0
+__global__ void pad_labels_kernel(const int* __restrict__ src, const long* __restrict__ offsets,
+                                  const int* __restrict__ lengths, int B, int Tmax, int* __restrict__ dst) {
+  const long n = (long)B * Tmax;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
+    const int t = (int)(e % Tmax), b = (int)(e / Tmax);
+    dst[e] = t < min(lengths[b], Tmax) ? src[offsets[b] + t] : 0;
+  }
+}
+
 // y = relu(x) ; dx = dy * 1[x > 0]
 __global__ void relu_fwd_kernel(const float* __restrict__ x, long n, float* __restrict__ y) {
   for (long e = blockIdx.x * 256L + threadIdx.x; e < n; e += (long)gridDim.x * 256) y[e] = fmaxf(x[e], 0.f);
@@ -545,6 +592,25 @@ int swap12(hipStream_t st, int B, int D1, int D2, int D3, const float* x, float*
   const long n = (long)B * D1 * D2 * D3;
   if (n <= 0) return 0;
   hipLaunchKernelGGL(swap12_kernel, dim3(grid1d(n)), dim3(256), 0, st, x, B, D1, D2, D3, y);
+  S2S_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int pad_batch(hipStream_t st, int B, int C, int Lmax, int F, const float* src, const long* offsets,
+              const int* lengths, float* dst) {
+  S2S_REQUIRE(B > 0 && C > 0 && Lmax > 0 && F > 0, "pad_batch: empty dims");
+  S2S_REQUIRE(B <= 65535, "pad_batch: B above the grid's 65535 utterances");
+  const long n = (long)C * Lmax * F;
+  hipLaunchKernelGGL(pad_batch_kernel, dim3(std::min(256u, grid1d(n, 1024)), (unsigned)B), dim3(256), 0, st, src,
+                     offsets, lengths, C, Lmax, F, dst);
+  S2S_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int pad_labels(hipStream_t st, int B, int Tmax, const int* src, const long* offsets, const int* lengths, int* dst) {
+  S2S_REQUIRE(B > 0 && Tmax > 0, "pad_labels: empty dims");
+  hipLaunchKernelGGL(pad_labels_kernel, dim3(grid1d((long)B * Tmax)), dim3(256), 0, st, src, offsets, lengths, B, Tmax,
+                     dst);
   S2S_CHECK_HIP(hipGetLastError());
   return 0;
 }

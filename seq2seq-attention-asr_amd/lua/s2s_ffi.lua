@@ -70,6 +70,8 @@ int s2s_smaxpool_bwd(s2s_ctx* ctx, s2s_stream_t stream, int B, int C, int H, int
 int s2s_swap12(s2s_ctx* ctx, s2s_stream_t stream, int B, int D1, int D2, int D3, const float* x, float* y);
 int s2s_relu_fwd(s2s_ctx* ctx, s2s_stream_t stream, long n, const float* x, float* y);
 int s2s_relu_bwd(s2s_ctx* ctx, s2s_stream_t stream, long n, const float* x, const float* dy, float* dx);
+int s2s_pad_batch(s2s_ctx* ctx, s2s_stream_t stream, int B, int C, int Lmax, int F, const float* src, const long* offsets, const int* lengths, float* dst);
+int s2s_pad_labels(s2s_ctx* ctx, s2s_stream_t stream, int B, int Tmax, const int* src, const long* offsets, const int* lengths, int* dst);
 int s2s_logsoftmax_fwd(s2s_ctx* ctx, s2s_stream_t stream, long rows, int n, const float* x, float* y);
 int s2s_logsoftmax_bwd(s2s_ctx* ctx, s2s_stream_t stream, long rows, int n, const float* y, const float* dy, float* dx);
 int s2s_nll_seed(s2s_ctx* ctx, s2s_stream_t stream, int B, int T, int O, const float* logp, const int* labels, const int* label_lengths, int normalize, float* nll, float* dlogp);

@@ -164,6 +164,9 @@ SIGNATURES = [
     ("s2s_smaxpool_bwd", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                  c_void_p, c_void_p, c_void_p]),
     ("s2s_swap12", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("s2s_pad_batch", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                              c_void_p]),
+    ("s2s_pad_labels", c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("s2s_relu_fwd", c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
     ("s2s_relu_bwd", c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
     ("s2s_logsoftmax_fwd", c_int, [c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p]),

@@ -169,3 +169,90 @@ def synthetic_corpus(n, F=80, O=29, L_range=(60, 120), T_range=(10, 30), eos=Non
         tree[f"{i}/x"] = x
         tree[f"{i}/chars"] = y.astype(np.int64)
     return tree
+
+
+class PackedUtterances:
+    """A corpus split packed once onto the device, and its padded batches assembled there (s2s_pad_batch /
+    s2s_pad_labels: one launch each per batch, no per-utterance host copies).
+
+    xs[i]: (L_i, F) frames, or (C, L_i, F) planes (the VGG front-end's layout) -- tensors or arrays, every
+    utterance with the same F (and C); ys[i]: (T_i,) 0-based labels.  Frames are concatenated into one flat float32
+    device tensor, labels into one int32 tensor; the upload happens at the first batch()."""
+
+    def __init__(self, xs, ys, device=None):
+        import torch
+        from .nn import S2SArgumentError
+        if len(xs) == 0 or len(xs) != len(ys):
+            raise S2SArgumentError(f"PackedUtterances: {len(xs)} utterances with {len(ys)} label sequences")
+        self._xs = [torch.as_tensor(x) for x in xs]
+        self._ys = [torch.as_tensor(y).reshape(-1) for y in ys]
+        nd = self._xs[0].dim()
+        if nd not in (2, 3):
+            raise S2SArgumentError("PackedUtterances: utterances are (L, F) or (C, L, F)")
+        self.planes = nd == 3
+        self.C = int(self._xs[0].shape[0]) if self.planes else 1
+        self.F = int(self._xs[0].shape[-1])
+        for x, y in zip(self._xs, self._ys):
+            if x.dim() != nd or int(x.shape[-1]) != self.F or (self.planes and int(x.shape[0]) != self.C):
+                raise S2SArgumentError("PackedUtterances: every utterance needs the same layout, C and F")
+            if x.shape[-2] < 1 or x.numel() == 0 or y.numel() < 1:
+                raise S2SArgumentError("PackedUtterances: an utterance needs at least 1 frame and 1 label")
+        self.Ls = [int(x.shape[-2]) for x in self._xs]
+        self.Ts = [int(y.numel()) for y in self._ys]
+        self.device = device
+        self.x = None
+
+    def __len__(self):
+        return len(self.Ls)
+
+    def _upload(self):
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device()) if self.device is None else torch.device(self.device)
+        xo = np.concatenate([[0], np.cumsum([self.C * L * self.F for L in self.Ls])[:-1]]).astype(np.int64)
+        yo = np.concatenate([[0], np.cumsum(self.Ts)[:-1]]).astype(np.int64)
+        self.x = torch.cat([x.to(dev, torch.float32).reshape(-1) for x in self._xs])
+        self.y = torch.cat([y.to(dev, torch.int32) for y in self._ys])
+        self.x_off, self.y_off = torch.from_numpy(xo).to(dev), torch.from_numpy(yo).to(dev)
+        self._xs = self._ys = None
+        self.device = dev
+
+    def batch(self, idx, Lmax=None, Tmax=None, out=None):
+        """The padded batch of utterances idx: (x (B, Lmax, F) or (B, C, Lmax, F), y (B, Tmax) int32, frame
+        DeviceLengths, label DeviceLengths, Ls, Ts); padding frames and labels are 0.  Lmax / Tmax default to the
+        longest of the batch.  out = an earlier result of the same B, Lmax, Tmax: its buffers and lengths are
+        refilled in place (the buffers a captured step reads) and returned."""
+        import torch
+        from .nn import DeviceLengths, S2SArgumentError, check, dptr, get_context, lib, stream_ptr
+        idx = [int(i) for i in idx]
+        if not idx or min(idx) < 0 or max(idx) >= len(self.Ls):
+            raise S2SArgumentError("PackedUtterances.batch: utterance index out of range")
+        Ls, Ts = [self.Ls[i] for i in idx], [self.Ts[i] for i in idx]
+        B = len(idx)
+        if out is not None:
+            x, y, fl, tl = out[:4]
+            if x.shape[0] != B or y.shape[0] != B or (Lmax or x.shape[-2]) != x.shape[-2] or \
+                    (Tmax or y.shape[1]) != y.shape[1]:
+                raise S2SArgumentError("PackedUtterances.batch: out has another padded shape")
+            Lmax, Tmax = int(x.shape[-2]), int(y.shape[1])
+        Lmax, Tmax = int(Lmax or max(Ls)), int(Tmax or max(Ts))
+        if max(Ls) > Lmax or max(Ts) > Tmax:
+            raise S2SArgumentError(f"PackedUtterances.batch: lengths must be in [1, {Lmax}] frames and [1, {Tmax}] "
+                                   "labels")
+        if self.x is None:
+            self._upload()
+        dev = self.device
+        if out is None:
+            shape = (B, self.C, Lmax, self.F) if self.planes else (B, Lmax, self.F)
+            x = torch.empty(shape, dtype=torch.float32, device=dev)
+            y = torch.empty((B, Tmax), dtype=torch.int32, device=dev)
+            fl, tl = DeviceLengths(Ls, Lmax, dev), DeviceLengths(Ts, Tmax, dev)
+        else:
+            fl.fill_(Ls)
+            tl.fill_(Ts)
+        sel = torch.tensor(idx, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        ctx = get_context(dev.index).handle
+        xo, yo = self.x_off[sel], self.y_off[sel]  # (alive until both launches are issued)
+        check(lib.s2s_pad_batch(ctx, stream_ptr(), B, self.C, Lmax, self.F, dptr(self.x), dptr(xo), dptr(fl.tensor),
+                                dptr(x)))
+        check(lib.s2s_pad_labels(ctx, stream_ptr(), B, Tmax, dptr(self.y), dptr(yo), dptr(tl.tensor), dptr(y)))
+        return x, y, fl, tl, Ls, Ts

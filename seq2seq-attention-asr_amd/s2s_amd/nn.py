@@ -191,6 +191,63 @@ def lengths_tensor(lengths, n, maxlen, device):
     return tc.to(torch.int32).to(device)
 
 
+class DeviceLengths:
+    """Per-utterance lengths that live on the device: `values` (n of them, each in [1, maxlen]) are checked once on
+    the host and kept in a persistent (n,) int32 tensor whose pointer never changes.  BiRNN.lengths,
+    Attention.frame_lengths / label_lengths and nll_seed take one as is (no copy, no host check, no
+    synchronisation), so a captured step reads the lengths at replay time: fill_() new values of the same count in
+    place and replay.  derive() keeps lengths computed from these (a front-end's output lengths) in step."""
+
+    def __init__(self, values, maxlen, device=None):
+        self.maxlen = int(maxlen)
+        vals = self._check(values, None)
+        self.n = len(vals)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.tensor = torch.empty(self.n, dtype=torch.int32, device=dev)
+        self._derived = {}
+        self._put(vals)
+
+    def _check(self, values, n):
+        t = torch.as_tensor(values).to(torch.int64).reshape(-1).cpu()
+        if t.numel() == 0 or (n is not None and t.numel() != n):
+            raise S2SArgumentError(f"lengths: {t.numel()} values for {n if n is not None else 'at least 1'} utterances")
+        if int(t.min()) < 1 or int(t.max()) > self.maxlen:
+            raise S2SArgumentError(f"lengths must be in [1, {self.maxlen}]")
+        return t.tolist()
+
+    def _put(self, vals):
+        self.values = vals
+        if self.tensor.is_cuda:
+            # a fresh pinned source per refill: the caching host allocator keeps it until the copy has run
+            self.tensor.copy_(torch.tensor(vals, dtype=torch.int32).pin_memory(), non_blocking=True)
+        else:
+            self.tensor.copy_(torch.tensor(vals, dtype=torch.int32))
+
+    def fill_(self, values):
+        """New values of the same count, in place, on the current stream (derived lengths follow)."""
+        vals = self._check(values, self.n)
+        derived = [(d, d._check(fn(vals), d.n)) for (d, fn) in self._derived.values()]  # all checked before any write
+        self._put(vals)
+        for d, v in derived:
+            d._put(v)
+        return self
+
+    def derive(self, key, fn, maxlen):
+        """The DeviceLengths holding fn(values) (in [1, maxlen]), created once per (key, maxlen) and refilled by
+        every fill_() of this one."""
+        got = self._derived.get((key, int(maxlen)))
+        if got is None:
+            got = (DeviceLengths(fn(self.values), maxlen, self.tensor.device), fn)
+            self._derived[(key, int(maxlen))] = got
+        return got[0]
+
+    def ptr(self, n, maxlen):
+        """The device pointer, for n utterances of at most maxlen (two host integer compares, no device work)."""
+        if self.n != n or self.maxlen > maxlen:
+            raise S2SArgumentError(f"lengths: {self.n} values in [1, {self.maxlen}] for {n} utterances of {maxlen}")
+        return self.tensor.data_ptr()
+
+
 def _uniform(shape, stdv, gen=None):
     return (torch.rand(shape, generator=gen, dtype=torch.float64) * 2 - 1).mul_(stdv).float()
 
@@ -333,6 +390,8 @@ class _GruSeq(Module):
     def _lengths_ptr(self, B, L, dev):
         if self.lengths is None:
             return ctypes.c_void_p(0)
+        if isinstance(self.lengths, DeviceLengths):
+            return ctypes.c_void_p(self.lengths.ptr(B, L))
         self._len_dev = lengths_tensor(self.lengths, B, L, dev)
         return dptr(self._len_dev)
 
@@ -581,11 +640,15 @@ class Attention(Module):
 
     def _set_lengths(self, d, B, L, T, dev):
         self._len_keep = []
-        if self.frame_lengths is not None:
+        if isinstance(self.frame_lengths, DeviceLengths):
+            d.frame_lengths = self.frame_lengths.ptr(B, L)
+        elif self.frame_lengths is not None:
             t = lengths_tensor(self.frame_lengths, B, L, dev)
             self._len_keep.append(t)
             d.frame_lengths = t.data_ptr()
-        if self.label_lengths is not None:
+        if isinstance(self.label_lengths, DeviceLengths):
+            d.label_lengths = self.label_lengths.ptr(B, T)
+        elif self.label_lengths is not None:
             t = lengths_tensor(self.label_lengths, B, T, dev)
             self._len_keep.append(t)
             d.label_lengths = t.data_ptr()
@@ -882,9 +945,13 @@ def nll_seed(logp, labels, normalize=False, label_lengths=None):
     lab = labels.to(torch.int32).contiguous()
     nll = torch.empty(B, device=logp.device, dtype=torch.float32)
     dlogp = torch.empty_like(logp)
-    tl = lengths_tensor(label_lengths, B, T, logp.device) if label_lengths is not None else None
+    if isinstance(label_lengths, DeviceLengths):
+        tlp = ctypes.c_void_p(label_lengths.ptr(B, T))
+    else:
+        tl = lengths_tensor(label_lengths, B, T, logp.device) if label_lengths is not None else None
+        tlp = dptr(tl)
     check(lib.s2s_nll_seed(get_context(logp.device.index).handle, stream_ptr(), B, T, O, dptr(logp), dptr(lab),
-                           dptr(tl), int(normalize), dptr(nll), dptr(dlogp)))
+                           tlp, int(normalize), dptr(nll), dptr(dlogp)))
     return nll, dlogp
 
 
