@@ -181,6 +181,11 @@ typedef struct {
    * MonotonicAlignment gradient at steps >= T_b; the caller's dlogp must be 0 there, s2s_nll_seed does it) */
   const int* frame_lengths;
   const int* label_lengths;
+  /* beam search with hybrid attention (read by the s2s_attn_beam_* entry points only; s2s_model_attn_dims sets
+   * 0).  0: every hypothesis row keeps a private copy of h and Vh, and frame_lengths is an error.  1: the
+   * hypotheses of an utterance share its h and Vh, as content attention's always do (only ws and alpha_{t-1}
+   * are per hypothesis), and frame_lengths is accepted.  Without hybrid attention it changes nothing. */
+  int beam_share_hybrid;
 } s2s_attn_dims;
 #define S2S_ATTN_NPARAMS_LSTM 36
 size_t s2s_attn_saved_bytes(const s2s_attn_dims* d);
@@ -223,8 +228,10 @@ const int* s2s_attn_maxout_argmax(const s2s_attn_dims* d, const void* saved);
  * hidden {alpha, s, mem}, Attention.lua:360-403), fused decoder_mlp.
  * Content attention shares each utterance's Vh and h among its hypotheses: the workspace holds no copy of h, so
  * h must stay valid until the search has finished.  It also takes a padded batch: with frame_lengths (B),
- * frames >= L_b of utterance b get no attention weight.  frame_lengths with hybrid attention is an error
- * (search such an utterance's own frames); label_lengths is ignored. */
+ * frames >= L_b of utterance b get no attention weight.  Hybrid attention does both with beam_share_hybrid = 1
+ * (alpha_{t-1} is 0 past L_b, so the location filter sees the zero padding of an utterance of L_b frames);
+ * with beam_share_hybrid = 0 it keeps a copy of h and Vh per hypothesis row in the workspace, and frame_lengths
+ * with hybrid attention is an error (search such an utterance's own frames).  label_lengths is ignored. */
 size_t s2s_attn_beam_workspace_bytes(const s2s_attn_dims* d, int K, int maxseqlength);
 int s2s_attn_beam_search(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, const float* h,
                          const float* const* params, int eos, int K, int maxseqlength, int* out, int ldo, int* out_len,

@@ -49,6 +49,10 @@ struct AttnDims {
   // utterances, Vh is kept once per utterance (vh_rows, L, Sc), and only the per-step forward kernels' buffers
   // are laid out -- no backward working set, no persistent-kernel granules
   int vh_rows = 0;
+  // beam search with hybrid attention (s2s_attn_dims::beam_share_hybrid): 1 = the hypotheses of an utterance share
+  // its Vh and h as content attention's do (only ws and alpha_{t-1} stay per hypothesis) and flen is accepted;
+  // 0 = one private copy per hypothesis row, flen refused.  Read by the beam entry points only.
+  int share_hybrid = 0;
 };
 int set_device_u64(hipStream_t st, unsigned long long* p, unsigned long long v);
 constexpr int kMaxHybK = 8;  // largest hybrid filter served (the reference's fallback model uses 5)
@@ -118,7 +122,8 @@ const float* attn_saved_dropout_mask(const AttnDims& d, const void* saved);
 // (B, ldo >= maxlen + 1) best hypothesis per utterance (tokens, -1 padded), out_len, out_score (its
 // summed log-probability).  Synchronises the stream (stops when every utterance has K finished).
 size_t attn_beam_workspace_bytes(const AttnDims& d, int K, int maxlen);
-// d.flen (content attention only): frames >= L_b of utterance b take no part.  maxlens (device, B, or null):
+// d.flen (content attention, or hybrid with d.share_hybrid): frames >= L_b of utterance b take no part.  maxlens
+// (device, B, or null):
 // each utterance's own hypothesis length limit, clamped to [1, maxlen].  h must stay valid until the search ends.
 int attn_beam_search(hipStream_t st, const AttnDims& d, const float* h, const AttnParams& P, int eos, int K,
                      int maxlen, const int* maxlens, int* out, int ldo, int* out_len, float* out_score, void* ws,

@@ -2131,11 +2131,18 @@ constexpr int kBeamMaxK = 16;
 // hypotheses' ws before the next one is fetched, and the context loop's hv[LC] registers are reused per row.
 // Per (row, frame) the sums run in dec_f2_attn's order (lane-strided float4 columns, wave_sum, context in
 // frame order).  Frames l >= L_b score -inf and weigh 0; a chunk wholly past L_b writes PM = -inf, PL = PC = 0.
-template <int WV>
+// HYB (hybrid location-aware attention): what stays per hypothesis is ws and alpha_{t-1}.  The chunk's alpha_{t-1}
+// halo of every active row (the row's t = 0 ALPHA slot, filled by beam_prep; 0 outside [0, L), as hyb_stage_alpha
+// stages one row's) waits in LDS, and a lane's HCU and tap float4s of HGT are loaded once for all hypotheses.  Per
+// (row, frame): u = HCU + sum_i HGT_i apl[j][li + i] (taps in order, hyb_uf4_lds), z = (ws_j + Vh) + u, as
+// dec_f2_attn forms them.  alpha is 0 past L_b (E = -inf there), so the halo reads the zero padding the reference
+// applies to an utterance of L_b frames.
+template <int WV, bool HYB>
 __global__ __launch_bounds__(64 * WV) void beam_f2_shared(AttnK k, BeamK q) {
   constexpr int FPW = LC / WV, NT = 64 * WV;
   __shared__ float sc[kBeamMaxK][LC];
   __shared__ float pw[kBeamMaxK][LC];
+  __shared__ float apl[HYB ? kBeamMaxK : 1][LC + kMaxHybK];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ch = blockIdx.x, b = blockIdx.y;
   if (q.done[b]) return;
@@ -2144,6 +2151,15 @@ __global__ __launch_bounds__(64 * WV) void beam_f2_shared(AttnK k, BeamK q) {
   const int Lb = q.frames ? min(q.frames[b], L) : L;
   const float* we = k.P.we;
   const float* ws0 = k.WS + ((long)b * K * 2 + 1) * Sc;  // row r's ws_t at ws0 + j * 2 * Sc (t = 1 of T = 2)
+  const int kw = HYB ? min(k.hk, kMaxHybK) : 0;
+  if constexpr (HYB) {
+    const int pl = hyb_pad_left(kw), n = LC + kw - 1;
+    for (int x = tid; x < na * n; x += NT) {
+      const int j = x / n, i = x - j * n, m = ch * LC + i - pl;
+      apl[j][i] = (m >= 0 && m < L) ? k.ALPHA[((long)(b * K + j) * 2) * L + m] : 0.f;
+    }
+    __syncthreads();
+  }
   for (int i = 0; i < FPW; ++i) {
     const int li = wave * FPW + i, l = ch * LC + li;
     float part[kBeamMaxK];
@@ -2154,12 +2170,37 @@ __global__ __launch_bounds__(64 * WV) void beam_f2_shared(AttnK k, BeamK q) {
       for (int c4 = lane; c4 < Sc / 4; c4 += 64) {
         const float4 v = reinterpret_cast<const float4*>(vh)[c4];
         const float4 e = reinterpret_cast<const float4*>(we)[c4];
+        if constexpr (HYB) {
+          const float4 hc = reinterpret_cast<const float4*>(k.HCU)[c4];
+          float4 g[kMaxHybK];
 #pragma unroll
-        for (int j = 0; j < kBeamMaxK; ++j) {
-          if (j < na) {
-            const float4 w = reinterpret_cast<const float4*>(ws0 + (long)j * 2 * Sc)[c4];
-            const float4 z = make_float4(w.x + v.x, w.y + v.y, w.z + v.z, w.w + v.w);
-            part[j] += e.x * tanhf(z.x) + e.y * tanhf(z.y) + e.z * tanhf(z.z) + e.w * tanhf(z.w);
+          for (int i = 0; i < kMaxHybK; ++i)
+            g[i] = i < kw ? reinterpret_cast<const float4*>(k.HGT + (long)i * Sc)[c4] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+          for (int j = 0; j < kBeamMaxK; ++j) {
+            if (j < na) {
+              const float4 w = reinterpret_cast<const float4*>(ws0 + (long)j * 2 * Sc)[c4];
+              float4 z = make_float4(w.x + v.x, w.y + v.y, w.z + v.z, w.w + v.w);
+              float4 u = hc;
+#pragma unroll
+              for (int i = 0; i < kMaxHybK; ++i) {
+                if (i < kw) {
+                  const float a = apl[j][li + i];
+                  u.x += g[i].x * a; u.y += g[i].y * a; u.z += g[i].z * a; u.w += g[i].w * a;
+                }
+              }
+              z.x += u.x; z.y += u.y; z.z += u.z; z.w += u.w;
+              part[j] += e.x * tanhf(z.x) + e.y * tanhf(z.y) + e.z * tanhf(z.z) + e.w * tanhf(z.w);
+            }
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < kBeamMaxK; ++j) {
+            if (j < na) {
+              const float4 w = reinterpret_cast<const float4*>(ws0 + (long)j * 2 * Sc)[c4];
+              const float4 z = make_float4(w.x + v.x, w.y + v.y, w.z + v.z, w.w + v.w);
+              part[j] += e.x * tanhf(z.x) + e.y * tanhf(z.y) + e.z * tanhf(z.z) + e.w * tanhf(z.w);
+            }
           }
         }
       }
@@ -2424,9 +2465,10 @@ __global__ void edit_distance_kernel(int n, const int* a, const int* alen, int l
 // s2s_debug_beam_replicate(1): content attention also takes the replicated path (A/B arm, tests); a search must
 // run start to end under one setting, since the workspace layout follows it
 std::atomic<int> g_beam_replicate{0};
-// Content attention shares each utterance's Vh and h among its hypotheses (beam_f2_shared); hybrid attention
-// keeps one private copy per hypothesis row (its location features come from the row's own alpha_{t-1})
-bool beam_shared(const AttnDims& d) { return d.hf == 0 && !g_beam_replicate.load(); }
+// Content attention shares each utterance's Vh and h among its hypotheses (beam_f2_shared); hybrid attention does
+// when the caller opts in (AttnDims::share_hybrid: only ws and alpha_{t-1} are per hypothesis) and otherwise keeps
+// one private copy per hypothesis row
+bool beam_shared(const AttnDims& d) { return (d.hf == 0 || d.share_hybrid) && !g_beam_replicate.load(); }
 
 AttnDims beam_dims(const AttnDims& d, int K) {
   AttnDims d2 = d;
@@ -2455,9 +2497,10 @@ BeamLayout beam_layout(const AttnDims& d, int K, int maxlen) {
   l.state = l.scratch + up(attn_scratch_bytes(d2));
   const size_t ints = 2 /*hptr*/ + 4 * (size_t)d.B + R /*yprev*/ + 2 * R * L1 /*hist*/ + 2 * R /*hlen*/ +
                       R * L1 /*fseq*/ + R /*flen*/ + 2 * R /*lab2*/;
-  // alpha_{t-1} per hypothesis only feeds hybrid attention's location features
+  // alpha_{t-1} per hypothesis only feeds hybrid attention's location features: the shared content layout has none
   // (the LSTM cell only with an LSTM decoder)
-  const size_t floats = R /*pbeam*/ + 2 * R * d.S /*s*/ + R /*fscore*/ + (shared ? 0 : 2 * R * d.L) /*alpha*/ +
+  const size_t floats = R /*pbeam*/ + 2 * R * d.S /*s*/ + R /*fscore*/ +
+                        (shared && d.hf == 0 ? 0 : 2 * R * d.L) /*alpha*/ +
                         (d.lstm ? 2 * R * d.S : 0) /*mem*/ + R * (size_t)(d.S + d.A) /*mlp_in*/;
   l.fstate = l.state + up(4 * ints);
   l.total = l.fstate + up(4 * floats);
@@ -2483,8 +2526,9 @@ static int beam_view(const AttnDims& d, const AttnParams& P, int eos, int K, int
   S2S_TRY(attn_check_dims(d));
   S2S_REQUIRE(K >= 1 && K <= kBeamMaxK && K <= d.O, "beam search: K must be in [1, 16] and <= outputDepth");
   S2S_REQUIRE(maxlen >= 1 && eos >= 0 && eos < d.O, "beam search: bad eos / maxlen");
-  S2S_REQUIRE(!d.flen || d.hf == 0,
-              "beam search: frame lengths unsupported with hybrid attention (search an utterance's own frames)");
+  S2S_REQUIRE(!d.flen || d.hf == 0 || d.share_hybrid,
+              "beam search: frame lengths unsupported with hybrid attention unless beam_share_hybrid is set "
+              "(search an utterance's own frames)");
   S2S_REQUIRE(!d.flen || beam_shared(d), "beam search: frame lengths need the shared-annotation path");
   const BeamLayout bl = beam_layout(d, K, maxlen);
   S2S_REQUIRE(ws && ws_bytes >= bl.total, "beam search: workspace too small");
@@ -2516,7 +2560,7 @@ static int beam_view(const AttnDims& d, const AttnParams& P, int eos, int K, int
   q.pbeam = fp; fp += R;
   q.s = fp; fp += 2L * R * S;
   q.fscore = fp; fp += R;
-  q.alpha = fp; fp += v.d2.vh_rows > 0 ? 0 : 2L * R * d.L;
+  q.alpha = fp; fp += v.d2.vh_rows > 0 && d.hf == 0 ? 0 : 2L * R * d.L;
   q.mem = fp; fp += d.lstm ? 2L * R * S : 0;
   q.mlp_in = fp;
   v.k.P = P;
@@ -2578,7 +2622,8 @@ int attn_beam_step(hipStream_t st, const AttnDims& d, const AttnParams& P, int K
   decide("beam.layout.overlay", v.overlay ? 1 : 0);  // the step's post-combine buffers live inside PC (carve)
   // 16 waves, one frame each: a wave scores its frame for up to K hypotheses in turn, so the serial chain per
   // launch is K frames' worth where dec_f2_attn<8>'s is 2 (the wave count does not change a bit of the results)
-  if (shared) hipLaunchKernelGGL(beam_f2_shared<16>, dim3(k.NCH, d.B), dim3(1024), 0, st, k, v.q);
+  const auto f2 = d.hf > 0 ? beam_f2_shared<16, true> : beam_f2_shared<16, false>;
+  if (shared) hipLaunchKernelGGL(f2, dim3(k.NCH, d.B), dim3(1024), 0, st, k, v.q);
   else hipLaunchKernelGGL(dec_f2_attn<8>, dim3(k.NCH, R), dim3(512), 0, st, k);
   hipLaunchKernelGGL(dec_f3_combine, dim3(R), dim3(256), 0, st, k);
   hipLaunchKernelGGL(dec_f4_cin, dim3(S / 16, bt), dim3(256), 0, st, k);

@@ -57,6 +57,7 @@ AttnDims to_attn(const s2s_attn_dims* d) {
   a.lstm = d->decoder_lstm ? 1 : 0;
   a.flen = d->frame_lengths;
   a.tlen = d->label_lengths;
+  a.share_hybrid = d->beam_share_hybrid ? 1 : 0;
   return a;
 }
 

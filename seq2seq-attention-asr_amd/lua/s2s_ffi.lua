@@ -34,7 +34,7 @@ size_t s2s_lstm_saved_bytes(int B, int L, int H);
 size_t s2s_lstm_scratch_bytes(int ndir, int B, int L, int D, int H, int peepholes);
 int s2s_lstm_fwd(s2s_ctx* ctx, s2s_stream_t stream, int ndir, int B, int L, int D, int H, int peepholes, const int* reverse, const float* x, long ldx, const float* const* W, float* const* y, long ldy, void* const* saved, const int* lengths, void* scratch, size_t scratch_bytes);
 int s2s_lstm_bwd(s2s_ctx* ctx, s2s_stream_t stream, int ndir, int B, int L, int D, int H, int peepholes, const int* reverse, const float* x, long ldx, const float* const* W, void* const* saved, const float* const* dy, long lddy, float* dx, long lddx, int dx_accumulate, float* const* dW, float scale, const int* lengths, void* scratch, size_t scratch_bytes);
-typedef struct { int B, L, T; int annotationDepth, scoreDepth, stateDepth, outputDepth, mlpDepth, maxoutWindow; float penalty; float dropout; unsigned long long dropout_seed; const float* dropout_mask; int hybridAttendFilterSize, hybridAttendFeatureMaps; int external_mlp; int decoder_lstm; const int* frame_lengths; const int* label_lengths; } s2s_attn_dims;
+typedef struct { int B, L, T; int annotationDepth, scoreDepth, stateDepth, outputDepth, mlpDepth, maxoutWindow; float penalty; float dropout; unsigned long long dropout_seed; const float* dropout_mask; int hybridAttendFilterSize, hybridAttendFeatureMaps; int external_mlp; int decoder_lstm; const int* frame_lengths; const int* label_lengths; int beam_share_hybrid; } s2s_attn_dims;
 size_t s2s_attn_saved_bytes(const s2s_attn_dims* d);
 size_t s2s_attn_scratch_bytes(const s2s_attn_dims* d);
 int s2s_attn_fwd(s2s_ctx* ctx, s2s_stream_t stream, const s2s_attn_dims* d, const float* h, const int* labels, const float* const* params, float* logp, void* saved, void* scratch, size_t scratch_bytes);

@@ -27,7 +27,7 @@ class s2s_attn_dims(ctypes.Structure):
                 ("penalty", c_float), ("dropout", c_float), ("dropout_seed", ctypes.c_ulonglong),
                 ("dropout_mask", c_void_p), ("hybridAttendFilterSize", c_int), ("hybridAttendFeatureMaps", c_int),
                 ("external_mlp", c_int), ("decoder_lstm", c_int), ("frame_lengths", c_void_p),
-                ("label_lengths", c_void_p)]
+                ("label_lengths", c_void_p), ("beam_share_hybrid", c_int)]
 
 
 class s2s_optim_config(ctypes.Structure):

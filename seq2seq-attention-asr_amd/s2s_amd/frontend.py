@@ -627,8 +627,9 @@ class RaggedModel:
 
     def BeamSearch(self, eos, K=5, maxseqlength=None, frame_lengths=None, maxseqlengths=None):
         """decoder:BeamSearch(encoder.output, eos, K, maxseqlen) on the annotations of the last step / forward.
-        frame_lengths (B,): annotation frames L'_b of a padded batch (content attention only: the hybrid decoder
-        refuses them -- Evaluate searches equal-L' groups instead).  Returns (tokens (B, maxseqlength + 1) padded
+        frame_lengths (B,): annotation frames L'_b of a padded batch (content attention, or a hybrid decoder with
+        decoder.share_hybrid_search on; otherwise the hybrid decoder refuses them and Evaluate searches equal-L'
+        groups instead).  Returns (tokens (B, maxseqlength + 1) padded
         with -1, lengths (B), scores (B))."""
         h = self.encoder.output
         if h is None:
@@ -736,7 +737,7 @@ class VGGAttentionModel(RaggedModel, GraphStep, Module):
     maxlen_factor = 2   # librispeech/train.lua:251: the search runs to twice the utterance's input frames
 
     def _search(self, h, Lp, limits, eos, K):
-        """One ragged search over the padded annotations (content attention: frames >= L'_b take no part)."""
+        """One ragged search over the padded annotations (frames >= L'_b take no part)."""
         out, olen, osc = self.decoder.BeamSearch(h, eos, K, max(limits), frame_lengths=Lp, maxseqlengths=limits)
         self.eval_groups.append((None, list(range(h.shape[0]))))
         return out, olen, osc
@@ -772,8 +773,11 @@ class ConvBiLSTMAttentionModel(RaggedModel, GraphStep, Module):
     maxlen_factor = 1   # timit/timit.lua:400: the search runs to the utterance's own frame count
 
     def _search(self, h, Lp, limits, eos, K):
-        """Hybrid attention takes no frame lengths in the search, and three halvings leave few distinct L': the
-        annotation rows are gathered by equal L' into unpadded (B_g, L', A) groups, one search per group."""
+        """By default hybrid attention takes no frame lengths in the search, and three halvings leave few distinct
+        L': the annotation rows are gathered by equal L' into unpadded (B_g, L', A) groups, one search per group.
+        With decoder.share_hybrid_search the padded batch is searched in one ragged call, as the VGG model's is."""
+        if self.decoder.share_hybrid_search:
+            return VGGAttentionModel._search(self, h, Lp, limits, eos, K)
         B, dev = h.shape[0], h.device
         maxlen = max(limits)
         out = torch.full((B, maxlen + 1), -1, dtype=torch.int32, device=dev)

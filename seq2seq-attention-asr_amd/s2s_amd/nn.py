@@ -637,6 +637,9 @@ class Attention(Module):
     # variable-length batch: (B,) frames of h and labels per utterance (None = all L / T)
     frame_lengths = None
     label_lengths = None
+    # BeamSearch with hybrid attention: True = the hypotheses of an utterance share its Vh and h (only ws and
+    # alpha_{t-1} stay per hypothesis) and frame_lengths is accepted (s2s_attn_dims.beam_share_hybrid)
+    share_hybrid_search = False
 
     def _set_lengths(self, d, B, L, T, dev):
         self._len_keep = []
@@ -769,8 +772,9 @@ class Attention(Module):
         scores (B)).  maxseqlength defaults to L (:337).  Content or hybrid attention, GRU or LSTM
         decoder_recurrent; an external decoder_mlp runs between the search's step and advance calls on
         the (B*K, S+A) hypothesis rows.
-        frame_lengths (B,): a padded batch -- frames >= L_b of utterance b take no part (content attention only;
-        the module's training attribute frame_lengths is never used here).  maxseqlengths (B,): each utterance's
+        frame_lengths (B,): a padded batch -- frames >= L_b of utterance b take no part (content attention, or
+        hybrid attention with share_hybrid_search on; the module's training attribute frame_lengths is never used
+        here).  maxseqlengths (B,): each utterance's
         own length limit, in [1, maxseqlength]; defaults to frame_lengths when those are given (timit.lua:400
         searches each utterance to its own frame count).  finished=True (a diagnostic) also returns every finished
         hypothesis, the reference's y_finished / p_finished (:375-376), in finishing order: (nfin (B), flen (B, K),
@@ -792,6 +796,7 @@ class Attention(Module):
         finally:
             self.train = was_train
             self.frame_lengths, self.label_lengths = was_len
+        d.beam_share_hybrid = int(bool(self.share_hybrid_search))
         dev = h.device
         self._sync_pad()
         params = self._ptrs(False)
@@ -898,15 +903,15 @@ class BeamRun:
 def beam_search_call(ctx, d, h, params, eos, K, maxlen, frame_lengths=None, maxseqlengths=None, launch=True):
     """The one place a search's arguments are prepared (Attention.BeamSearch, ChorowskiBaseline.BeamSearch): d is
     the decoder's s2s_attn_dims for h (B, L, A) with no lengths set; frame_lengths (B,) in [1, L] go into it
-    (refused with hybrid attention), maxseqlengths (B,) in [1, maxlen] default to them; workspace and outputs are
+    (refused with hybrid attention unless d.beam_share_hybrid is set), maxseqlengths (B,) in [1, maxlen] default to them; workspace and outputs are
     allocated; with launch the whole search runs (s2s_attn_beam_search / _ragged), otherwise the caller steps it."""
     B, L, dev = h.shape[0], h.shape[1], h.device
     run = BeamRun()
     run.fl = run.mls = None
     if frame_lengths is not None:
-        if d.hybridAttendFeatureMaps > 0:
-            raise S2SArgumentError("BeamSearch: frame_lengths with hybrid attention is unsupported "
-                                   "(search such an utterance's own frames)")
+        if d.hybridAttendFeatureMaps > 0 and not d.beam_share_hybrid:
+            raise S2SArgumentError("BeamSearch: frame_lengths with hybrid attention needs share_hybrid_search "
+                                   "(or search such an utterance's own frames)")
         run.fl = lengths_tensor(frame_lengths, B, L, dev)
         d.frame_lengths = run.fl.data_ptr()
         if maxseqlengths is None:

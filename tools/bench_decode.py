@@ -8,10 +8,16 @@
   (c) ChorowskiBaseline.forward against the full step at config 2 (B = 32, L = 128, T = 40), graph mode: this
       build's step and, with --parent-lib, the older build's s2s_model_step on a graph-mode context of its own.
 
+  (d) the conv + BiLSTM model's decoder (timit/timit.lua:126-145: LSTM(400, 400), A = 256, scoreDepth 150 on 160
+      channels, hybrid attention kW = 5 / 16 maps, external decoder_mlp through the stepwise entry points), B = 32,
+      K = 5: (i) equal lengths, share_hybrid_search on against off, with the workspace of each; (ii) mixed L', one
+      ragged call against the equal-L' groups ConvBiLSTMAttentionModel._search runs by default.
+
 Every arm is warmed up, timed with device events around the whole call (the search's own host polls included),
 and the arms alternate inside one process, `--repeats` times each.  Prints one JSON object and writes it to --out.
 
-  python tools/bench_decode.py --out profiles/decode/bench_decode.json [--parent-lib /path/to/libs2s_hip.so]
+  python tools/bench_decode.py --out profiles/decode/bench_decode.json --skip d [--parent-lib /path/to/libs2s_hip.so]
+  python tools/bench_decode.py --out profiles/decode/bench_decode_hybrid.json --skip a,b,c
 """
 import argparse
 import ctypes
@@ -156,12 +162,69 @@ def alternate(arms, repeats, warmup=2):
             for n, v in ms.items()}, last
 
 
+def hybrid_arm(s2s_amd, _lib, rng, repeats, B=32, K=5, L=60):
+    """Arm (d): the conv + BiLSTM model's own decoder module, searched with share_hybrid_search on and off."""
+    model = s2s_amd.ConvBiLSTMAttentionModel(123, 62, generator=torch.Generator().manual_seed(1)).cuda()
+    att, eos = model.decoder, 61
+    with torch.no_grad():  # as decoder_params: searches over log-probabilities that are not uniform
+        att.own["we"].mul_(3.0)
+        att.own["Wy"].mul_(3.0)
+        att.own["hybU"].mul_(4.0)
+        [m for m in att.decoder_mlp.modules if hasattr(m, "weight")][-1].weight.mul_(3.0)
+    dev = att.own["V"].device
+    h = torch.tensor(rng.standard_normal((B, L, 256)) * 1.5, dtype=torch.float32, device=dev)
+
+    def search(on, *a, **k):
+        att.share_hybrid_search = on
+        try:
+            return att.BeamSearch(*a, **k)
+        finally:
+            att.share_hybrid_search = False
+
+    def ws_bytes(on):
+        d = att._dims(h, 1)
+        d.beam_share_hybrid = int(on)
+        return int(_lib.lib.s2s_attn_beam_workspace_bytes(ctypes.byref(d), K, L))
+
+    t, last = alternate({"shared": lambda: search(True, h, eos, K, L),
+                         "replicated": lambda: search(False, h, eos, K, L)}, repeats)
+    sh, rp = last["shared"], last["replicated"]
+    same = bool(torch.equal(sh[0], rp[0]) and torch.equal(sh[1], rp[1]))
+    out = {"decoder": dict(S=400, A=256, Sc=160, kW=5, maps=16, lstm=True, external_mlp=True), "B": B, "K": K,
+           "i_equal_length": dict(L=L, arms=t, tokens_equal=same,
+                                  scores_bitwise_equal=bool(torch.equal(sh[2], rp[2])),
+                                  mean_prediction_length=float(sh[1].float().mean()),
+                                  workspace_bytes={"shared": ws_bytes(True), "replicated": ws_bytes(False)})}
+    # (ii) L' of 32 utterances with raw frames uniform in [120, 480] behind the front-end's three halvings
+    Lp = sorted(int(x) // 8 for x in rng.integers(120, 481, B))
+    limits = [8 * lp for lp in Lp]
+    hm = torch.tensor(rng.standard_normal((B, max(Lp), 256)) * 1.5, dtype=torch.float32, device=dev)
+
+    def model_search(on):
+        att.share_hybrid_search, model.eval_groups = on, []
+        try:
+            return model._search(hm, Lp, limits, eos, K)
+        finally:
+            att.share_hybrid_search = False
+
+    t, last = alternate({"ragged_one_call": lambda: model_search(True), "equal_Lp_groups": lambda: model_search(False)},
+                        repeats, warmup=1)
+    rg, gr = last["ragged_one_call"], last["equal_Lp_groups"]
+    same = sum(int(rg[1][i]) == int(gr[1][i]) and torch.equal(rg[0][i, :int(rg[1][i])], gr[0][i, :int(gr[1][i])])
+               for i in range(B))
+    out["ii_mixed_lengths"] = dict(Lp=Lp, groups=len(set(Lp)), arms=t, identical_predictions=same,
+                                   mean_prediction_length=float(rg[1].float().mean()),
+                                   ratio_groups_over_ragged=round(
+                                       t["equal_Lp_groups"]["median_ms"] / t["ragged_one_call"]["median_ms"], 3))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--parent-lib", default=None, help="libs2s_hip.so of the build to compare against")
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--skip", default="", help="comma list of a,b,c")
+    ap.add_argument("--skip", default="", help="comma list of a,b,c,d")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_decode needs a GPU"
     import s2s_amd
@@ -241,6 +304,8 @@ def main():
         if args.parent_lib:  # the same step: the older build's logp equals this build's full step's bit for bit
             res["c_forward_only"]["parent_logp_bitwise_equal"] = bool(torch.equal(last["parent_full_step"],
                                                                                    last["full_step"][1]))
+    if "d" not in skip:
+        res["d_hybrid_conv_decoder"] = hybrid_arm(s2s_amd, _lib, rng, args.repeats)
     line = json.dumps(res)
     print(line)
     if args.out:

@@ -10,6 +10,9 @@ the whole call:
             surface: model.step(x[None], y[None]) per utterance for training; encoder.forward + decoder.forward +
             nll_seed + decoder.BeamSearch(h, eos, K, limit) per utterance for validation
 
+For the conv + BiLSTM model a third measurement times Evaluate with decoder.share_hybrid_search on (one ragged
+search per padded batch) against off (one search per equal-L' group), and reports whether the two agree.
+
 No threshold is attached to these numbers; they are written down (--out, default
 profiles/models_ragged/bench.json) so that the next change can be measured against them.
 
@@ -89,10 +92,29 @@ def bench_model(kind, args):
             nll_seed(logp, y[None])
             model.decoder.BeamSearch(h[0], eos, args.K, factor * x.shape[axis])
 
+    def eval_shared():
+        model.decoder.share_hybrid_search = True
+        try:
+            return model.Evaluate(pk, None, K=args.K, max_batch=args.max_batch)
+        finally:
+            model.decoder.share_hybrid_search = False
+
+    def eval_grouped():
+        return model.Evaluate(pk, None, K=args.K, max_batch=args.max_batch)
+
     out = {"model": kind, "utterances": N, "frames": [int(x.shape[axis]) for x in xs],
            "labels": [int(y.numel()) for y in ys], "K": args.K, "max_batch": args.max_batch, "reps": args.reps}
-    for name, arms in (("step_ragged_epoch_slice", (("ragged", train_ragged), ("loop", train_loop))),
-                       ("evaluate", (("ragged", eval_ragged), ("loop", eval_loop)))):
+    measurements = [("step_ragged_epoch_slice", (("ragged", train_ragged), ("loop", train_loop))),
+                    ("evaluate", (("ragged", eval_ragged), ("loop", eval_loop)))]
+    if kind == "conv":
+        measurements.append(("evaluate_share_hybrid_search", (("shared", eval_shared), ("grouped", eval_grouped))))
+        sh, gr = eval_shared(), eval_grouped()
+        out["evaluate_share_hybrid_search_agreement"] = {
+            "identical_predictions": sum(a.tolist() == b.tolist() for a, b in zip(sh[3], gr[3])),
+            "per_shared": sh[2], "per_grouped": gr[2]}
+    if args.only:
+        measurements = [m for m in measurements if m[0] in args.only.split(",")]
+    for name, arms in measurements:
         for _, fn in arms:
             fn()  # warm-up: lazily grown buffers, first-launch costs
         ms = {a: [] for a, _ in arms}
@@ -100,7 +122,8 @@ def bench_model(kind, args):
             for a, fn in arms:
                 ms[a].append(timed(fn))
         out[name] = {a: {"median_ms": statistics.median(v), "all_ms": v} for a, v in ms.items()}
-        out[name]["speedup_loop_over_ragged"] = out[name]["loop"]["median_ms"] / out[name]["ragged"]["median_ms"]
+        (new, _), (base, _) = arms
+        out[name][f"speedup_{base}_over_{new}"] = out[name][base]["median_ms"] / out[name][new]["median_ms"]
         print(name, kind, {a: round(out[name][a]["median_ms"], 1) for a in ms}, flush=True)
     return out
 
@@ -112,6 +135,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--max-batch", type=int, default=32)
     ap.add_argument("--K", type=int, default=5)
+    ap.add_argument("--only", default="", help="comma list of measurements to run (default: all)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "models_ragged", "bench.json"))
     args = ap.parse_args()
     import torch
