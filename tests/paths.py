@@ -75,8 +75,8 @@ class Reader:
         self._frozen = snap
 
 
-# every name the library records (csrc: attn.hip, gru.hip, gru_persist.hip, lstm.hip, lstm_persist.hip,
-# model_step.cpp), for the snapshot a reader keeps after its block
+# every name the library records (csrc: attn.hip and its beam.inc, gru.hip, gru_persist.hip, lstm.hip,
+# lstm_persist.hip, model_step.cpp), for the snapshot a reader keeps after its block
 NAMES = (
     "dec.fwd.path", "dec.bwd.path", "dec.var", "dec.U", "dec.nchains", "dec.XLC", "dec.NCH", "dec.res",
     "dec.persist_res", "dec.allow_local", "dec.merged_head", "dec.head_bwd_fused", "dec.head_sums_slabs", "dec.r4",
