@@ -1519,9 +1519,11 @@ bool gru_persist_wgrad_fits(int ndir, int B, int H, int D) {
 bool gru_persist_supported(int ndir, int B, int H) {
   if (!(H == 64 || H == 128 || H == 256 || H == 512)) return false;
   const int MT = (B + 15) / 16;
-  // the chains placed on one XCD must be co-resident there (32 CUs, >= 2 workgroups per CU at
-  // this footprint): forward members 2H/16 per chain, chains (dir, tile) dealt 8 per round
-  return (2 * H / 16) * ((ndir * MT + 7) / 8) <= 64;
+  // the chains placed on one XCD must be co-resident there: forward members 2H/16 per chain, chains
+  // (dir, tile) dealt 8 per round, and one workgroup per CU (32 CUs; kFwdThreads = 320 is five waves at
+  // more than 128 registers, so a CU's eight wave slots hold one workgroup: launch_nc's check_resident
+  // refuses a grid above 256).  H = 512 (64 members per chain) therefore never runs persistently.
+  return (2 * H / 16) * ((ndir * MT + 7) / 8) <= 32;
 }
 
 static size_t census_bytes(int B, int H) { return 4 * (size_t)(2 * ((B + 15) / 16)) * (2 * H / 16); }

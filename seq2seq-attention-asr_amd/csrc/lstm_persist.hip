@@ -350,7 +350,8 @@ void carve_sync(char* sync, int B, int L, int H, int nchains, int nmem, LArgs& a
 bool lstm_persist_supported(int ndir, int B, int H, int peep) {
   const char* m = std::getenv("S2S_LSTM_MODE");
   if (m && std::strcmp(m, "step") == 0) return false;
-  if (peep || H % 64 != 0 || H > 256) return false;  // (H = 512: the backward's 16 weight chunks spill)
+  // only the widths lstm_persist_fwd / _bwd instantiate (H = 512: the backward's 16 weight chunks spill)
+  if (peep || !(H == 64 || H == 128 || H == 256)) return false;
   const int MT = (B + 15) / 16, nchains = ndir * MT, nmem = H / 16;
   // every member of the chains dealt to one XCD co-resident there, one per CU (32 CUs per XCD)
   return nmem * ((nchains + 7) / 8) <= 32;
