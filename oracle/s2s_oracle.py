@@ -465,11 +465,14 @@ def _gru_dec_bwd(P, G, Wg, g_, ds, sp, d, S, scale):
 
 
 def attention_bwd(P: Dict[str, Array], cfg: "ModelConfig", cache, dlogp: Array, G: Dict[str, Array],
-                  scale: float = 1.0, dropout_mask: Optional[Array] = None, dmlp_in: Optional[Array] = None):
+                  scale: float = 1.0, dropout_mask: Optional[Array] = None, dmlp_in: Optional[Array] = None,
+                  softmax_sum_via_context: bool = False):
     """nn.Attention:updateGradInput (Attention.lua:324-327): RNNAttention's reverse BPTT
     (RNNAttention.lua:203-253) accumulating d{Vh, h} over all t (:247); dy discarded
     (:248).  MonotonicAlignment.lua:44-77 adds lambda*(L+1-j)*ind to d alpha and its
-    negation to d alpha_prev.  Returns dh (B, L, A)."""
+    negation to d alpha_prev.  Returns dh (B, L, A).
+    softmax_sum_via_context: the softmax backward's sum_j alpha_j d alpha_j formed as dc . c plus the sum over the
+    carried terms (c = alpha^T h; the same number, another association) -- a restatement for float32 error floors."""
     h, Vh, labels = cache["h"], cache["Vh"], cache["labels"]
     B, L, A = h.shape
     T = (dlogp if dmlp_in is None else dmlp_in).shape[1]
@@ -549,9 +552,13 @@ def attention_bwd(P: Dict[str, Array], cfg: "ModelConfig", cache, dlogp: Array, 
         # MonotonicAlignment backward
         gdiff = cfg.penalty * jw[None, :] * g_("mono_ind")[:, None]
         dalpha = dalpha + gdiff
+        if softmax_sum_via_context:
+            ssum = np.sum(dc * c, 1, keepdims=True) + np.sum(alpha * (dalpha_carry + gdiff), 1, keepdims=True)
+        else:
+            ssum = np.sum(alpha * dalpha, 1, keepdims=True)
         dalpha_carry = -gdiff
         # softmax backward (3p)
-        de = alpha * (dalpha - np.sum(alpha * dalpha, 1, keepdims=True))
+        de = alpha * (dalpha - ssum)
         ws = g_("ws")
         Z = ws[:, None, :] + Vh
         if hyb:
